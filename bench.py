@@ -1,7 +1,14 @@
 """Benchmark: train examples/sec (fwd+bwd+update) of the relation-VAE training step.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3] [--batch-size 100]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...      (one process per GPU, RCCL)
+
+A plain run does what the headline figure needs and no more: set up, warm up, time the K steps
+(plus the row index's per-batch cost over one window, which the headline counts in), write the
+outputs if --dump-outputs is given, print the result line.  Everything under "Also reported"
+below runs only with --full.  K + W may exceed the epoch's batches: the step sequence then
+wraps to the epoch's first batch on the same negatives, as a further epoch would run it.
 
 A "step" is one func['train'] call on one global batch (l examples per rank): encoder +
 decoder forward/backward + AdaGrad update of every parameter.  Inputs (dataset, per-epoch
@@ -14,7 +21,12 @@ batches, running concurrently; shorter runs (the driver's 20 steps) time the ste
 add the index at its serial per-batch cost measured over a whole window; value =
 K * global_batch / seconds -- end-to-end training throughput.  Rank 0 prints one JSON line.
 
-Also reported: the roofline of the step's dominant kernel (the one with the longest average
+--dump-outputs DIR writes what the timed path left after its last step, as DIR/<name>.npy
+(float32): the per-batch costs of the timed steps and every parameter and AdaGrad accumulator
+the step updates (dump_outputs).  The inputs are seeded, so two builds run with the same
+arguments can be compared output for output.
+
+Also reported (--full): the roofline of the step's dominant kernel (the one with the longest average
 launch; algorithmic bytes per launch by SURVEY.md 8(d)'s accounting / its average duration
 from HIP events on the launch stream), both kernels' lines, and the CPU baseline -- the
 reference's dense Theano schedule restated in torch (oracle/cpu_ref.py), float64 and float32,
@@ -217,17 +229,59 @@ def cpu_baseline(data, cfg, l, budget_s, max_steps=200):
                 ms_per_step=1e3 * l / runs[best]["value"])
 
 
+def batch_spans(start, count, nb):
+    """[(first batch, batches), ...] of `count` consecutive steps from step `start` of a
+    sequence that wraps to batch 0 after the epoch's nb batches (one span within an epoch)."""
+    out, b = [], start % nb
+    while count > 0:
+        n = min(count, nb - b)
+        out.append((b, n))
+        count -= n
+        b = 0
+    return out
+
+
+DUMP_SAMPLE = 1 << 19       # elements written of a larger array (fixed, seeded positions)
+
+
+def dump_outputs(path, eng, model, W, K):
+    """What the training path holds after its last timed step, as <path>/<name>.npy (float32):
+    `costs`, the per-batch costs of the timed steps in step order (the last epoch's worth when
+    the steps wrapped), and every parameter (`W`, `Wb`, `A`, `Ab`, `C1`/`C2`/`R`/`C`) and its
+    AdaGrad accumulator (`acc_<name>`) -- whole when it has at most DUMP_SAMPLE elements, else
+    the elements at DUMP_SAMPLE sorted positions of the flattened array drawn with replacement
+    from RandomState(1234) (duplicates dropped): the positions depend on the array's size alone,
+    so two runs write the same elements.  At most 14 arrays of 2 MiB plus the costs."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    n = min(K, eng.nb)
+    order = (W + np.arange(K - n, K)) % eng.nb
+    np.save(os.path.join(path, "costs.npy"), eng.costs.cpu().numpy()[order].astype(np.float32))
+    arrays = dict(model.named_params())
+    arrays.update({f"acc_{k}": v for k, v in eng._acc.items()})
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            pos = np.unique(np.random.RandomState(1234).randint(0, flat.numel(), DUMP_SAMPLE))
+            flat = flat[torch.as_tensor(pos, device=flat.device)]
+        np.save(os.path.join(path, f"{name}.npy"), flat.float().cpu().numpy())
+
+
 def warm_up(eng, W, K, prebuilt, graphed):
     """Capture every graph the warm-up and the timed steps replay (no capture inside the timed
     region), then run the W warm-up steps.  A step with a collective the runtime cannot capture
     (data-parallel exchange) falls back to eager launches; returns whether graphs are used.
     (tests/test_dist.py::test_rccl_one_rank_captured_exchange exercises the fallback.)"""
     import torch
+    wspans, tspans = batch_spans(0, W, eng.nb), batch_spans(W, K, eng.nb)
     try:
         if graphed:
-            eng.capture_for(0, W)
-            eng.capture_for(W, K, last_advance=False)
-        eng.run(0, W, index=not prebuilt)
+            for b, n in wspans:
+                eng.capture_for(b, n)
+            for i, (b, n) in enumerate(tspans):
+                eng.capture_for(b, n, last_advance=i + 1 < len(tspans))
+        for b, n in wspans:
+            eng.run(b, n, index=not prebuilt)
     except RuntimeError as e:              # e.g. a collective the runtime cannot capture
         if eng.exchange is None or not graphed:
             raise
@@ -238,7 +292,8 @@ def warm_up(eng, W, K, prebuilt, graphed):
         eng._graphs.clear()
         eng.cursor_moved()
         torch.cuda.synchronize()
-        eng.run(0, W, index=not prebuilt)
+        for b, n in wspans:
+            eng.run(b, n, index=not prebuilt)
     return graphed
 
 
@@ -247,6 +302,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=512)
     ap.add_argument("--warmup", type=int, default=64)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed (costs, parameters, "
+                         "accumulators: dump_outputs) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline run also measure the per-kernel durations and "
+                         "rooflines, the labelling pass, the HBM copy and bf16 MFMA ceilings and "
+                         "the CPU baseline (the options below that name them apply to --full)")
     ap.add_argument("--no-index-overlap", action="store_true",
                     help="build each window's row index on the step stream (serial, counted at "
                          "its per-batch cost) instead of beside the previous window's steps")
@@ -273,6 +335,8 @@ def main():
                     help="--dp-xchg p2p with ranks on different GPUs (verified on ranks sharing "
                          "one GPU only; refused without this flag)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.dp_xchg != "collective":
         args.dp_update = "partitioned"
         args.kernel_form.append(f"dp_xchg={args.dp_xchg}")
@@ -315,12 +379,11 @@ def main():
     eng.sample_epoch_negatives(ind.negativeSampler, "device")
     torch.cuda.synchronize()
     t_neg = time.perf_counter() - t0
-    neg1, neg2 = eng.neg1.cpu().numpy(), eng.neg2.cpu().numpy()
     rdist.warm_up(exchange, eng.exchange_buf)
     nb = eng.nb
     K, W = args.steps, args.warmup
-    if K + W > nb:
-        raise SystemExit(f"steps+warmup={K + W} exceed the {nb} global batches of one epoch")
+    # steps past the epoch's last batch wrap to its first one on the same negatives
+    wrapped = K + W > nb
 
     # The per-batch row index (rae_build_index) depends only on the batch's ids, negatives and
     # CSR rows -- not on the parameters -- so the epoch loop builds it a window of batches
@@ -328,19 +391,22 @@ def main():
     # its per-batch cost over a whole window (how the epoch loop pays it) is added to the
     # timed seconds for the headline value.
     # (the pipelined peer-to-peer form's last step reads the row lists of the batch after it)
-    look = min(eng._look, nb - W - K)
-    prebuilt = W + K + look <= eng.index_window
+    look = max(0, min(eng._look, nb - W - K))
+    prebuilt = not wrapped and W + K + look <= eng.index_window
     if prebuilt:
         eng.build_index(0, W + K + look)
         eng.check()                        # a partition overflow is reported before any step
     if eng._dp:                            # the rows all-to-all's communicator, before capture
         if not prebuilt:
-            eng.build_index(0, min(eng.index_window, W + K))
+            eng.build_index(0, min(eng.index_window, W + K, nb))
         if not eng._p2p:
             exchange.rows(eng._dp_send, eng._dp_recv)
         torch.cuda.synchronize()
     graphed = warm_up(eng, W, K, prebuilt, args.graph_chunk > 1)
-    timed_graphs = eng.graph_sizes(W, K) if graphed else []
+    tspans = batch_spans(W, K, nb)
+    timed_graphs = [g for b, n in tspans for g in eng.graph_sizes(b, n)] if graphed else []
+    if len(timed_graphs) > 64:             # a long run: the sizes and how often each is replayed
+        timed_graphs = {str(g): timed_graphs.count(g) for g in sorted(set(timed_graphs))}
     torch.cuda.synchronize()
     rdist.barrier()
     torch.cuda.synchronize()
@@ -355,16 +421,21 @@ def main():
     if prebuilt and eng.index_overlap and 2 * K <= eng.index_window and K >= OVERLAP_MIN_STEPS:
         npref = max(0, min(K, nb - W - K))
     # no run follows the timed one on this cursor: its last graph skips the cursor advance
-    eng.run(W, K, index=not prebuilt, last_advance=False,
-            prefetch=None if not prebuilt else npref > 0, sync_peers=False)
+    for i, (b, n) in enumerate(tspans):
+        eng.run(b, n, index=not prebuilt, last_advance=i + 1 < len(tspans),
+                prefetch=None if not prebuilt else npref > 0, sync_peers=False)
     t_host = time.perf_counter() - t0          # host time to queue the timed region's work
     torch.cuda.synchronize()
     rdist.barrier()
     torch.cuda.synchronize()
     elapsed = rdist.max_over_ranks(time.perf_counter() - t0)
     eng.check()
-    costs = eng.costs[W:W + K].cpu().numpy()
+    costs = (eng.costs[:nb] if wrapped else eng.costs[W:W + K]).cpu().numpy()
     assert np.all(np.isfinite(costs)), "non-finite cost"
+    if args.dump_outputs:
+        eng.sync_replicas()                # partitioned update: every row from its owner
+        if rk == 0:
+            dump_outputs(args.dump_outputs, eng, ind.modelFunc, W, K)
     # row-index build cost per batch, over one whole window (as the epoch loop builds it)
     st0 = torch.cuda.current_stream()
     nwin = min(eng.index_window, nb)
@@ -376,6 +447,72 @@ def main():
     index_us = ie[0].elapsed_time(ie[1]) * 1e3 / nwin
     index_us = rdist.max_over_ranks(index_us)
 
+    # headline: end-to-end training throughput with the row index counted in -- built inside
+    # the timed region beside the steps (npref batches), the rest at its serial cost
+    e2e = elapsed + ((K - npref) * index_us * 1e-6 if prebuilt else 0.0)
+    ms_per_step = 1e3 * e2e / K
+    out = {
+        "metric": METRIC,
+        "value": K * L / e2e,
+        "unit": "examples/s",
+        "n_gpus": ws,
+        "steps": K,
+        "warmup": W,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "bf16 MFMA operands, fp32 accumulate" if cfg.get("bf16") else "fp32",
+        "data": "synthetic (SURVEY 8d generator, seed 1234; random-init params, seed 2)",
+        "full": args.full,
+        "config": {"workload": cfg["name"], "global_batch": L, "batch_per_gpu": l,
+                   "n_examples": cfg["N"], "n_features": cfg["d"], "relations": cfg["m"],
+                   "embed": cfg["r"], "neg_samples": cfg["s"], "decoder": cfg["dec"],
+                   "optimizer": "adagrad", "parallelism": f"dp{ws}",
+                   "n_entities": data.get_arg_voc_size(),
+                   "graph_chunk": args.graph_chunk if graphed else 1,
+                   "timed_graph_steps": timed_graphs,
+                   "graph_batches": "absolute" if (graphed and eng.graph_absolute) else "cursor",
+                   "kernel_forms": eng.kernel_forms_in_use()},
+        "negative_sampling_s": t_neg,
+        "negative_sampling": "host RandomState uniforms (reference stream) + device CDF search",
+        "timed_region_host_queue_us": t_host * 1e6,
+        "index_build_us_per_batch": index_us,
+        "index_build": ("k_build_index + k_build_tasks (parameter-independent per-batch row "
+                        "index): the next batches' index built on a side stream beside the "
+                        "timed steps (index_batches_built_in_timed_region); batches it could "
+                        "not build there are counted at index_build_us_per_batch (serial, "
+                        "over a whole window)"),
+        "index_batches_built_in_timed_region": npref if prebuilt else K,
+        "index_overlap": eng.index_overlap,
+        "index_mode": ("beside the timed steps (side stream)" if npref > 0 else
+                       "serial, counted at index_build_us_per_batch per step") if prebuilt else
+                      "on the step stream before each window (inside the timed region)",
+        "epochs_wrapped": len(tspans) - 1,
+        "build_id": eng.lib.rae_build_id().decode(),
+        "dataset_build_s": t_data,
+    }
+    if eng._dp and not eng._p2p:
+        out["config"]["dp_row_caps"] = list(eng._dp_caps)
+    if args.dump_outputs:
+        out["dump_outputs"] = args.dump_outputs
+    if args.full:
+        out.update(full_measurements(args, cfg, data, ind, eng, exchange, dev, W, K, rk, out["value"]))
+    if rk == 0:
+        print(json.dumps(out), flush=True)
+    eng.close()
+    if ws > 1:
+        import torch.distributed as dist
+        dist.destroy_process_group()
+
+
+def full_measurements(args, cfg, data, ind, eng, exchange, dev, W, K, rk, value):
+    """The --full run's further measurements, taken after the headline's timed region on the
+    same engine: per-kernel durations and rooflines, the labelling pass, the HBM copy and bf16
+    MFMA ceilings, and (one rank) the CPU baseline.  Returns the result line's further keys."""
+    import torch
+    nb, l, L, ws = eng.nb, eng.l, eng.L, eng.world_size
+    neg1, neg2 = eng.neg1.cpu().numpy(), eng.neg2.cpu().numpy()
     # ---- per-kernel durations: eager launches of the same step sequence continuing the
     # epoch, each phase launched through rae_time_next (hipExtLaunchKernelGGL), so the HIP
     # events carry the kernels' own dispatch begin/end timestamps -- the span rocprofv3
@@ -383,7 +520,7 @@ def main():
     lib, plan = eng.lib, eng.plan
     st = torch.cuda.current_stream()
     sp_ = C.c_void_p(st.cuda_stream)
-    b0 = W + K
+    b0 = (W + K) % nb
     n_it = min(args.kernel_iters, nb - b0, eng.index_window)
     eng.build_index(b0, n_it)
     eng.set_cursor(b0)
@@ -590,32 +727,7 @@ def main():
         if roof.get("unit") == "TFLOP/s" and cfg.get("bf16"):
             roof["frac_of_measured_peak"] = roof["achieved"] / mfma_peak["TFLOPs"]
 
-    # headline: end-to-end training throughput with the row index counted in -- built inside
-    # the timed region beside the steps (npref batches), the rest at its serial cost
-    e2e = elapsed + ((K - npref) * index_us * 1e-6 if prebuilt else 0.0)
-    ms_per_step = 1e3 * e2e / K
     out = {
-        "metric": METRIC,
-        "value": K * L / e2e,
-        "unit": "examples/s",
-        "n_gpus": ws,
-        "steps": K,
-        "warmup": W,
-        "ms_per_step": ms_per_step,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "bf16 MFMA operands, fp32 accumulate" if cfg.get("bf16") else "fp32",
-        "data": "synthetic (SURVEY 8d generator, seed 1234; random-init params, seed 2)",
-        "config": {"workload": cfg["name"], "global_batch": L, "batch_per_gpu": l,
-                   "n_examples": cfg["N"], "n_features": cfg["d"], "relations": cfg["m"],
-                   "embed": cfg["r"], "neg_samples": cfg["s"], "decoder": cfg["dec"],
-                   "optimizer": "adagrad", "parallelism": f"dp{ws}",
-                   "n_entities": data.get_arg_voc_size(),
-                   "graph_chunk": args.graph_chunk if graphed else 1,
-                   "timed_graph_steps": timed_graphs,
-                   "graph_batches": "absolute" if (graphed and eng.graph_absolute) else "cursor",
-                   "kernel_forms": eng.kernel_forms_in_use()},
         "roofline": roof,
         "kernels": kern,
         "kernel_us": {"forward": fwd_us, "update": upd_us,
@@ -624,38 +736,16 @@ def main():
         "label_pass": label,
         "hbm_copy": hbm_copy,
         "mfma_bf16_peak": mfma_peak,
-        "negative_sampling_s": t_neg,
-        "negative_sampling": "host RandomState uniforms (reference stream) + device CDF search",
-        "timed_region_host_queue_us": t_host * 1e6,
-        "index_build_us_per_batch": index_us,
-        "index_build": ("k_build_index + k_build_tasks (parameter-independent per-batch row "
-                        "index): the next batches' index built on a side stream beside the "
-                        "timed steps (index_batches_built_in_timed_region); batches it could "
-                        "not build there are counted at index_build_us_per_batch (serial, "
-                        "over a whole window)"),
-        "index_batches_built_in_timed_region": npref if prebuilt else K,
-        "index_overlap": eng.index_overlap,
-        "index_mode": ("beside the timed steps (side stream)" if npref > 0 else
-                       "serial, counted at index_build_us_per_batch per step") if prebuilt else
-                      "on the step stream before each window (inside the timed region)",
-        "build_id": build_id,
-        "dataset_build_s": t_data,
     }
     if xch_ms is not None:
         out["kernel_us"]["exchange"] = float(np.mean(xch_ms) * 1e3)
     if eng._dp and not eng._p2p:
         out["kernel_us"]["row_pull"] = float(np.mean([a.elapsed_time(b) for a, b in pev]) * 1e3)
-        out["config"]["dp_row_caps"] = list(eng._dp_caps)
     if rk == 0 and ws == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(data, cfg, l, args.cpu_seconds)
         out["cpu_baseline"]["host_cpus"] = os.cpu_count()
-        out["speedup_vs_cpu"] = out["value"] / out["cpu_baseline"]["value"]
-    if rk == 0:
-        print(json.dumps(out), flush=True)
-    eng.close()
-    if ws > 1:
-        import torch.distributed as dist
-        dist.destroy_process_group()
+        out["speedup_vs_cpu"] = value / out["cpu_baseline"]["value"]
+    return out
 
 
 if __name__ == "__main__":

@@ -1,15 +1,18 @@
 """Test infrastructure: regenerate tests/golden/c1_sample.npz, BASELINE config 1's dataset.
 
-data-sample.txt (the reference's sample input, /root/reference/data-sample.txt) run through
-this repo's ingestion (rae.preprocess: OiePreprocessor.py's two passes, threshold 0) into the
-array layout of rae.data.save_npz: the train split's CSR features, entity ids, per-entity
-mention counts and the gold labels.  The GPU box has no /root/reference, so the GPU C1 test
-reads this fixture; tests/test_preprocess.py re-derives it here and checks it is unchanged.
+data-sample.txt (the reference's sample input, tests/golden/data-sample.txt.gz) run
+through this repo's ingestion (rae.preprocess: OiePreprocessor.py's two passes, threshold 0)
+into the array layout of rae.data.save_npz: the train split's CSR features, entity ids,
+per-entity mention counts and the gold labels.  The GPU C1 test reads this fixture;
+tests/test_preprocess.py re-derives it from the stored sample and checks it is unchanged.
 
-    python oracle/gen_c1_fixture.py [/root/reference/data-sample.txt]
+    python oracle/gen_c1_fixture.py [data-sample.txt or data-sample.txt.gz]
 """
+import gzip
 import os
+import shutil
 import sys
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "relation-autoencoder_amd"))
@@ -18,11 +21,17 @@ from rae.data import save_npz  # noqa: E402
 from rae.preprocess import FeatureLexicon, build_feature_lexicon, get_basic_clean_features, \
     index_dataset, load_features, read_examples  # noqa: E402
 
-SAMPLE = "/root/reference/data-sample.txt"
+SAMPLE = os.path.join(ROOT, "tests", "golden", "data-sample.txt.gz")
 OUT = os.path.join(ROOT, "tests", "golden", "c1_sample.npz")
 
 
 def build(path=SAMPLE):
+    if path.endswith(".gz"):                       # read_examples takes a plain text file
+        with tempfile.TemporaryDirectory() as tmp:
+            plain = os.path.join(tmp, "data-sample.txt")
+            with gzip.open(path, "rb") as src, open(plain, "wb") as dst:
+                shutil.copyfileobj(src, dst)
+            return build(plain)
     raw = read_examples(path)
     fx, lex = get_basic_clean_features(), FeatureLexicon()
     examples, labels = [], {}

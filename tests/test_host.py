@@ -115,6 +115,47 @@ def test_bench_attaches_traffic_of_the_same_batch_size():
     assert bench.pmc_traffic("c3", 37) is None
 
 
+def test_bench_steps_wrap_over_the_epoch():
+    """--steps beyond the epoch's batches: the step sequence wraps to batch 0 (bench.batch_spans),
+    every span inside the epoch, the counts summing to the steps asked for."""
+    import bench
+    assert bench.batch_spans(5, 20, 10000) == [(5, 20)]
+    assert bench.batch_spans(0, 0, 10) == []
+    assert bench.batch_spans(6, 4, 10) == [(6, 4)]                  # ends on the last batch
+    assert bench.batch_spans(10, 5, 10) == [(0, 5)]                 # starts on the wrap
+    spans = bench.batch_spans(64, 25000, 10000)
+    assert spans == [(64, 9936), (0, 10000), (0, 5064)]
+    assert all(0 <= b and b + n <= 10000 for b, n in spans)
+
+
+def test_bench_dump_outputs_layout(tmp_path):
+    """--dump-outputs: float32 .npy files, costs in timed-step order, small arrays whole, large
+    ones at the same seeded positions on every call (bench.dump_outputs; CPU stand-ins for the
+    engine and the model)."""
+    import types
+    import torch
+    import bench
+    nb, W, K = 10, 3, 12                                   # 12 timed steps from batch 3: wraps
+    big = torch.arange(bench.DUMP_SAMPLE + 1000, dtype=torch.float32).reshape(-1, 4)
+    eng = types.SimpleNamespace(nb=nb, costs=torch.arange(nb, dtype=torch.float32),
+                                _acc={"W": big * 2})
+    model = types.SimpleNamespace(named_params=lambda: {"W": big, "Wb": torch.ones(7)})
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), eng, model, W, K)
+    got = {f: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(got) == ["W.npy", "Wb.npy", "acc_W.npy", "costs.npy"]
+    assert all(v.dtype == np.float32 for v in got.values())
+    # steps 2..11 of the timed ones survive in the cost buffer: batches 5..9, 0..4
+    np.testing.assert_array_equal(got["costs.npy"], [5, 6, 7, 8, 9, 0, 1, 2, 3, 4])
+    np.testing.assert_array_equal(got["Wb.npy"], np.ones(7))
+    w = got["W.npy"]                                       # values are their own flat positions
+    assert bench.DUMP_SAMPLE // 2 < w.size <= bench.DUMP_SAMPLE and np.all(np.diff(w) > 0)
+    np.testing.assert_array_equal(got["acc_W.npy"], 2 * w)
+    for f, v in got.items():
+        np.testing.assert_array_equal(v, np.load(tmp_path / "b" / f))
+    assert sum(v.nbytes for v in got.values()) <= 64 << 20
+
+
 def test_p2p_device_guard():
     """the peer-to-peer exchange refuses ranks on different GPUs unless asked
     (engine.check_p2p_devices, called by TrainEngine._p2p_setup with every rank's device)."""

@@ -3,10 +3,11 @@ restated, and BASELINE config 1 (data-sample.txt, m=10, r=10, s=5, l=100) end to
 CPU oracle -- the reference's own C1 is "plumbing, no GPU".
 
 The feature extractors are checked on a line written here (a made-up sentence in the Yao
-format), each expected value derived by hand from the cited reference lines.  data-sample.txt
-is read from /root/reference when present (this container); the GPU box only has the derived
-fixture tests/golden/c1_sample.npz (oracle/gen_c1_fixture.py), which is checked here to be
-exactly what the ingestion produces.  bow_clean's stopword list (nltk) is unpinned.
+format), each expected value derived by hand from the cited reference lines.  data-sample.txt,
+the reference's sample input, is stored as tests/golden/data-sample.txt.gz; the derived fixture
+tests/golden/c1_sample.npz (oracle/gen_c1_fixture.py), which the GPU C1 test reads, is checked
+here to be exactly what the ingestion produces from it.  bow_clean's stopword list (nltk) is
+unpinned.
 """
 import os
 
@@ -15,8 +16,7 @@ import pytest
 
 from conftest import GOLDEN, ROOT
 
-SAMPLE = "/root/reference/data-sample.txt"
-have_sample = pytest.mark.skipif(not os.path.exists(SAMPLE), reason="reference data absent")
+SAMPLE = os.path.join(GOLDEN, "data-sample.txt.gz")
 
 # path, e1, e2, types, trigger, doc, sentence, pos, label (+ newline, as read from a file)
 LINE = ["->nsubj->wrote->dobj->", "Ada Lovelace", "The Notes", "PERSON-WORK",
@@ -146,7 +146,6 @@ def test_json_file_round_trip_and_split_extension(tmp_path):
         P.main([str(src), str(out), "--batch", "dev"])
 
 
-@have_sample
 def test_data_sample_matches_committed_fixture():
     import sys
     sys.path.insert(0, os.path.join(ROOT, "oracle"))

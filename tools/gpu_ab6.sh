@@ -11,7 +11,7 @@ for f in "$@"; do
   kf=""; [ "$f" != default ] && kf="--kernel-form $f"
   t=$(echo $f | tr -c 'a-zA-Z0-9' _)
   (cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats -f csv -d $O/ab_${C}_$t -o run \
-    -- python3 $R/bench.py --config $C --no-cpu-baseline --no-label-pass $kf > $O/ab_${C}_$t.json 2> $O/ab_${C}_$t.err) \
+    -- python3 $R/bench.py --full --config $C --no-cpu-baseline --no-label-pass $kf > $O/ab_${C}_$t.json 2> $O/ab_${C}_$t.err) \
     || { echo "ab $C $f failed"; tail -20 $O/ab_${C}_$t.err; exit 1; }
   python3 -c "
 import json; d=json.load(open('$O/ab_${C}_$t.json'))

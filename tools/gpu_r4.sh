@@ -31,12 +31,12 @@ for st in "$@"; do
         || { echo tests failed; grep -E "FAILED|Error" $O/alltests.log | head -20; tail -5 $O/alltests.log; exit 1; }
       tail -2 $O/alltests.log ;;
     bench)
-      timeout -k 10 500 python3 -u bench.py > $O/bench.json 2> $O/bench.err \
+      timeout -k 10 500 python3 -u bench.py --full > $O/bench.json 2> $O/bench.err \
         || { echo bench failed; tail -30 $O/bench.err; exit 1; }
       python3 -c "import json; d=json.load(open('$O/bench.json')); print('c3', round(d['value']), 'us/step', round(d['ms_per_step']*1e3, 2), {k: round(v, 2) for k, v in d['kernel_us'].items()}, 'frac', round(d['roofline']['frac'], 3), 'cpu', d.get('cpu_baseline', {}).get('value'))" ;;
     bench:*)
       c=${st#bench:}
-      timeout -k 10 400 python3 -u bench.py --config $c --no-cpu-baseline --no-label-pass > $O/bench_$c.json 2> $O/bench_$c.err \
+      timeout -k 10 400 python3 -u bench.py --full --config $c --no-cpu-baseline --no-label-pass > $O/bench_$c.json 2> $O/bench_$c.err \
         || { echo $c bench failed; tail -20 $O/bench_$c.err; exit 1; }
       python3 -c "import json; d=json.load(open('$O/bench_$c.json')); print('$c', round(d['value']), 'us/step', round(d['ms_per_step']*1e3, 2), {k: round(v, 2) for k, v in d['kernel_us'].items()})" ;;
     dpmodel:*)
@@ -60,7 +60,7 @@ print('projection', {k: v for k, v in d['projection'].items() if k!='assumptions
     prof|prof:*)
       c=${st#prof}; c=${c#:}; c=${c:-c3}
       (cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats -f csv \
-        -d $O/prof_$c -o run -- python3 $R/bench.py --config $c --no-cpu-baseline --no-label-pass \
+        -d $O/prof_$c -o run -- python3 $R/bench.py --full --config $c --no-cpu-baseline --no-label-pass \
         > $O/prof_$c.json 2> $O/prof_$c.err) || { echo prof failed; tail -30 $O/prof_$c.err; exit 1; }
       cut -c1-120 $O/prof_$c/run_kernel_stats.csv | head -12 ;;
     *) echo "unknown step $st"; exit 2 ;;

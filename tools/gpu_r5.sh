@@ -32,24 +32,24 @@ for st in "$@"; do
       tail -2 $O/alltests.log ;;
     drv)
       # the driver's exact command (BENCH_rNN.json): 20 timed steps, 5 warm-up
-      timeout -k 10 500 python3 -u bench.py --gpus 1 --steps 20 --warmup 5 > $O/drv.json 2> $O/drv.err \
+      timeout -k 10 500 python3 -u bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/drv.json 2> $O/drv.err \
         || { echo drv bench failed; tail -30 $O/drv.err; exit 1; }
       python3 -c "import json; d=json.load(open('$O/drv.json')); print('drv', round(d['value']), 'us/step', round(d['ms_per_step']*1e3, 2), 'hostq', round(d['timed_region_host_queue_us'],1), {k: round(v, 2) for k, v in d['kernel_us'].items()}, 'cpu', d.get('cpu_baseline', {}).get('value'))" ;;
     drvq)
       # the driver's command without the CPU baseline / label pass (timing only)
-      timeout -k 10 300 python3 -u bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-label-pass > $O/drvq.json 2> $O/drvq.err \
+      timeout -k 10 300 python3 -u bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-label-pass > $O/drvq.json 2> $O/drvq.err \
         || { echo drvq bench failed; tail -30 $O/drvq.err; exit 1; }
       python3 -c "import json; d=json.load(open('$O/drvq.json')); print('drvq', round(d['value']), 'us/step', round(d['ms_per_step']*1e3, 2), 'hostq', round(d['timed_region_host_queue_us'],1), {k: round(v, 2) for k, v in d['kernel_us'].items()})" ;;
     rep:*)
       # the driver's command n times (timing only; "rep:3" or "rep:3:--no-index-overlap")
       a=${st#rep:}; n=${a%%:*}; x=""; [ "$a" != "$n" ] && x=${a#*:}
       for i in $(seq 1 $n); do
-        timeout -k 10 300 python3 -u bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-label-pass $x > $O/rep_$i.json 2> $O/rep_$i.err \
+        timeout -k 10 300 python3 -u bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-label-pass $x > $O/rep_$i.json 2> $O/rep_$i.err \
           || { echo rep bench failed; tail -30 $O/rep_$i.err; exit 1; }
         python3 -c "import json; d=json.load(open('$O/rep_$i.json')); print('rep $x', round(d['value']), 'us/step', round(d['ms_per_step']*1e3, 2), 'hostq', round(d['timed_region_host_queue_us'],1), 'idx', round(d['index_build_us_per_batch'], 3), {k: round(v, 2) for k, v in d['kernel_us'].items()})"
       done ;;
     b512)
-      timeout -k 10 300 python3 -u bench.py --no-cpu-baseline --no-label-pass > $O/b512.json 2> $O/b512.err \
+      timeout -k 10 300 python3 -u bench.py --full --no-cpu-baseline --no-label-pass > $O/b512.json 2> $O/b512.err \
         || { echo b512 bench failed; tail -30 $O/b512.err; exit 1; }
       python3 -c "import json; d=json.load(open('$O/b512.json')); print('b512', round(d['value']), 'us/step', round(d['ms_per_step']*1e3, 2), 'hostq', round(d['timed_region_host_queue_us'],1), {k: round(v, 2) for k, v in d['kernel_us'].items()})" ;;
     hosttrace)
@@ -58,12 +58,12 @@ for st in "$@"; do
         || { echo hosttrace failed; tail -30 $O/hosttrace.err; exit 1; }
       tail -25 $O/hosttrace.err ;;
     bench)
-      timeout -k 10 500 python3 -u bench.py > $O/bench.json 2> $O/bench.err \
+      timeout -k 10 500 python3 -u bench.py --full > $O/bench.json 2> $O/bench.err \
         || { echo bench failed; tail -30 $O/bench.err; exit 1; }
       python3 -c "import json; d=json.load(open('$O/bench.json')); print('c3', round(d['value']), 'us/step', round(d['ms_per_step']*1e3, 2), {k: round(v, 2) for k, v in d['kernel_us'].items()}, 'frac', round(d['roofline']['frac'], 3), 'cpu', d.get('cpu_baseline', {}).get('value'))" ;;
     bench:*)
       c=${st#bench:}
-      timeout -k 10 400 python3 -u bench.py --config $c --no-cpu-baseline --no-label-pass > $O/bench_$c.json 2> $O/bench_$c.err \
+      timeout -k 10 400 python3 -u bench.py --full --config $c --no-cpu-baseline --no-label-pass > $O/bench_$c.json 2> $O/bench_$c.err \
         || { echo $c bench failed; tail -20 $O/bench_$c.err; exit 1; }
       python3 -c "import json; d=json.load(open('$O/bench_$c.json')); print('$c', round(d['value']), 'us/step', round(d['ms_per_step']*1e3, 2), {k: round(v, 2) for k, v in d['kernel_us'].items()})" ;;
     dpmodel:*)
@@ -87,7 +87,7 @@ print('projection', {k: v for k, v in d['projection'].items() if k!='assumptions
     prof|prof:*)
       c=${st#prof}; c=${c#:}; c=${c:-c3}
       (cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats -f csv \
-        -d $O/prof_$c -o run -- python3 $R/bench.py --config $c --no-cpu-baseline --no-label-pass \
+        -d $O/prof_$c -o run -- python3 $R/bench.py --full --config $c --no-cpu-baseline --no-label-pass \
         > $O/prof_$c.json 2> $O/prof_$c.err) || { echo prof failed; tail -30 $O/prof_$c.err; exit 1; }
       cut -c1-120 $O/prof_$c/run_kernel_stats.csv | head -12 ;;
     *) echo "unknown step $st"; exit 2 ;;

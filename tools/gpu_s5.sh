@@ -17,10 +17,10 @@ if [ -n "${STAMPS:-}" ]; then
   grep -v amdgpu.ids $O/stamps.log
 fi
 if [ -n "${CFG:-}" ]; then      # the bench line of one config + rocprofv3 kernel stats of it
-  timeout -k 10 300 python3 -u bench.py --config $CFG --no-cpu-baseline --no-label-pass --steps 256 > $O/bench_$CFG.json 2> $O/bench_$CFG.err || { echo bench failed; tail -20 $O/bench_$CFG.err; exit 1; }
+  timeout -k 10 300 python3 -u bench.py --full --config $CFG --no-cpu-baseline --no-label-pass --steps 256 > $O/bench_$CFG.json 2> $O/bench_$CFG.err || { echo bench failed; tail -20 $O/bench_$CFG.err; exit 1; }
   python3 -c "import json; d=json.load(open('$O/bench_$CFG.json')); print('$CFG', round(d['value']), 'us/step', round(d['ms_per_step']*1e3, 2), {k: round(v, 2) for k, v in d['kernel_us'].items()})"
   cd /tmp && export TMPDIR=/tmp
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d $O/prof_$CFG -o run -- python3 $R/bench.py --config $CFG --no-cpu-baseline --no-label-pass --steps 64 --warmup 8 > $O/prof_$CFG.json 2> $O/prof_$CFG.err || { echo prof failed; tail -20 $O/prof_$CFG.err; exit 1; }
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d $O/prof_$CFG -o run -- python3 $R/bench.py --full --config $CFG --no-cpu-baseline --no-label-pass --steps 64 --warmup 8 > $O/prof_$CFG.json 2> $O/prof_$CFG.err || { echo prof failed; tail -20 $O/prof_$CFG.err; exit 1; }
   cut -c1-120 $O/prof_$CFG/run_kernel_stats.csv | head -12
   cd $R
 fi
