@@ -321,6 +321,49 @@ int rae_label(const int32_t* indptr, const int32_t* indices, const float* values
               const float* W, const float* Wb, int32_t relations, int64_t row0,
               int64_t nrows, int64_t* labels_out, float* probs_out, rae_stream_t stream);
 
+/* --- forward-only objective (no reference counterpart: the reference's Theano function fuses
+ * the update, learning/OieInduction.py:146-149) ------------------------------------------- */
+/* The data term of the objective over rows [row0, row0+nrows) of any CSR split at the current
+ * parameters, for 'sp', 'rescal' and 'rescal+sp'.  Plan-free like rae_label; every pointer is a
+ * device pointer except the struct itself.  Per example b the reference's all_scores grouped by
+ * example (learning/OieModel.py:80-90, the decoders' get_scores):
+ *     terms[b] = (pos_b, H_b, neg_b)
+ *     pos_b = logsig(u_b) + logsig(u_{l+b})        H_b = alpha * (-sum_k P log P)
+ *     neg_b = sum over the example's 2s negative scores g of logsig(-g)
+ * sums_out = the three column sums (S_pos, S_H, S_neg) in double; the data term of the cost is
+ *     -(S_pos + 2 S_H + S_neg) / (nrows * (4 + 2s))
+ * (the reference's denominator is l(4+2s), so this is the mean of the per-batch costs at any
+ * batch size).  The L1 / L2 regularisers are NOT included.  SP keeps the reference's
+ * A[args1]-twice behaviour (SelectionalPreferences.py:34-35); the hybrid uses A[args2].  Exact
+ * fp32 (v_mfma_f32_16x16x4_f32) whatever operands training ran with.
+ * An example's three terms are bitwise independent of row0, nrows and the other rows of the
+ * call; sums_out depends only on the term values and nrows (one partial per 1024 rows, added in
+ * row order, double).
+ * The call allocates nothing, never synchronises and is stream-ordered (capturable); it writes
+ * only terms_out, sums_out and workspace.  Arguments are checked before the first HIP call.
+ * nrows == 0 is valid (zero sums).  Shapes: relations <= 512 (a multiple of 4 above 128; <= 320
+ * for the bilinear decoders), embed <= 1024, at most 160 KiB of LDS per 16-example tile;
+ * W / C1 / C2 / R3 16-byte aligned when relations % 4 == 0, A when embed % 4 == 0.            */
+typedef struct rae_eval_args {
+    int32_t decoder;            /* RAE_DEC_*                                                 */
+    int32_t relations, embed, neg_samples;          /* m, r, s                               */
+    int64_t n_entities;
+    float   alpha;
+    const float *W, *Wb, *A, *Ab, *C1, *C2, *R3;    /* unused ones may be NULL               */
+    const int32_t *indptr, *indices; const float *values;   /* values may be NULL (binary)  */
+    const int32_t *args1, *args2;
+    const int32_t *neg1, *neg2; int64_t neg_stride; /* (s, >= row0+nrows): column = row index
+                                                       within the split                      */
+    int64_t row0, nrows;
+    float  *terms_out;          /* (nrows, 3) fp32, may be NULL                              */
+    double *sums_out;           /* 3 doubles                                                 */
+    void   *workspace; int64_t workspace_bytes;
+} rae_eval_args;
+/* bytes of workspace rae_eval_cost needs for these arguments (host only, no HIP call; -1 on a
+ * bad argument).  Independent of nrows: long ranges are processed in chunks.               */
+int64_t rae_eval_workspace_bytes(const rae_eval_args* a);
+int rae_eval_cost(const rae_eval_args* a, rae_stream_t stream);
+
 /* --- measurement helper (bench.py; no reference counterpart) ------------------------- */
 /* STREAM-style device copy of `bytes` (multiple of 16, 16-byte aligned pointers) with float4
  * loads and stores: the measured HBM ceiling bench.py reports next to the 8 TB/s spec.   */

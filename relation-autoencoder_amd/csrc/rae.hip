@@ -27,6 +27,7 @@
 #include "rae_sp_split.hpp"
 #include "rae_common.hpp"
 #include "rae_dp.hpp"
+#include "rae_eval.hpp"
 #include "rae_index.hpp"
 #include "rae_label.hpp"
 #include "rae_p2p.hpp"
@@ -580,6 +581,33 @@ __global__ __launch_bounds__(256) void k_mfma_probe(int64_t iters, float* sink) 
 #pragma unroll
     for (int c = 0; c < 8; ++c) t += acc[c][0] + acc[c][1] + acc[c][2] + acc[c][3];
     if ((threadIdx.x & 63) == 0) sink[blockIdx.x * 4 + (threadIdx.x >> 6)] = t;
+}
+
+// ---- forward-only objective (rae_eval.hpp) ----
+template <bool V4>
+__global__ __launch_bounds__(RAE_EV_BT) void k_eval_dec(EvalArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    eval_dec<V4>(a, reinterpret_cast<float*>(smem));
+}
+template <bool V4>
+__global__ __launch_bounds__(RAE_EV_BT) void k_eval_enc(EvalArgs a) { eval_enc<V4>(a); }
+template <bool V4>
+__global__ __launch_bounds__(RAE_EV_MTT) void k_eval_mt(EvalArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    eval_mt<V4>(a, reinterpret_cast<float*>(smem));
+}
+__global__ __launch_bounds__(RAE_EV_BT) void k_eval_blocksum(const float* terms, int n,
+                                                             double* partial) {
+    __shared__ double red[RAE_EV_NW * 3];
+    eval_blocksum(terms, n, partial, red);
+}
+// sums[c] (+)= the chunk's partials in block order (init: the first chunk sets)
+__global__ void k_eval_acc(const double* partial, int nblk, double* sums, int init) {
+    const int c = threadIdx.x;
+    if (blockIdx.x != 0 || c >= 3) return;
+    double t = init ? 0.0 : sums[c];
+    for (int b = 0; b < nblk; ++b) t += partial[b * 3 + c];
+    sums[c] = t;
 }
 
 __global__ void k_add_cursor(int64_t* cursor, int64_t count) {
@@ -1784,5 +1812,136 @@ extern "C" int rae_label(const int32_t* indptr, const int32_t* indices, const fl
         hipLaunchKernelGGL(k_label<false>, dim3((unsigned)blocks), dim3(RAE_BT), 0, (hipStream_t)stream,
                            indptr, indices, values, W, Wb, m, row0, nrows, labels, probs);
     HIPCHK(hipGetLastError());
+    return RAE_OK;
+}
+
+// ---- forward-only objective -----------------------------------------------------------------
+namespace {
+struct EvalLayout {
+    int64_t chunk;                           // examples per launch round
+    size_t o_partial, o_terms, o_P, o_v, o_w, total;
+};
+inline size_t ev_align(size_t x) { return (x + 255) & ~(size_t)255; }
+// argument check (host only) and the workspace layout
+int eval_check(const rae_eval_args* a, EvalLayout& L, bool need_buffers) {
+    if (!a) return fail(RAE_E_INVALID, "null argument");
+    if (a->decoder < 0 || a->decoder > 2) return fail(RAE_E_INVALID, "decoder must be 0..2");
+    const int m = a->relations, r = a->embed, s = a->neg_samples;
+    if (m < 1 || m > 512) return fail(RAE_E_INVALID, "relations must be in [1, 512]");
+    if ((m % 4) != 0 && m > 128)
+        return fail(RAE_E_INVALID, "relations must be a multiple of 4 above 128");
+    if (r < 1 || r > 1024) return fail(RAE_E_INVALID, "embed must be in [1, 1024]");
+    if (s < 1) return fail(RAE_E_INVALID, "neg_samples must be >= 1");
+    const bool bil = a->decoder != RAE_DEC_SP;
+    if (bil && eval_mt_lds_bytes(m) > 160 * 1024)
+        return fail(RAE_E_INVALID, "relations must be <= 320 for the bilinear decoders");
+    if (eval_dec_lds_floats(a->decoder, m, r) * 4 > 160 * 1024)
+        return fail(RAE_E_INVALID, "relations / embed need more than 160 KiB of LDS per tile");
+    L.chunk = bil ? RAE_EV_CHUNK_BIL : RAE_EV_CHUNK_SP;
+    const size_t ch = (size_t)L.chunk, r4 = (size_t)eval_r4(r);
+    size_t o = 0;
+    L.o_partial = o; o = ev_align(o + (ch / RAE_EV_SUMROWS) * 3 * sizeof(double));
+    L.o_terms = o;   o = ev_align(o + ch * 3 * sizeof(float));
+    L.o_P = o;       if (bil) o = ev_align(o + ch * m * sizeof(float));
+    L.o_v = o;       if (bil) o = ev_align(o + (size_t)eval_nbj(r) * ch * r4 * sizeof(float));
+    L.o_w = o;       if (bil) o = ev_align(o + (size_t)eval_nbi(r) * ch * r4 * sizeof(float));
+    L.total = o;
+    if (!need_buffers) return RAE_OK;
+    if (a->n_entities < 1 || a->n_entities >= (1ll << 31))
+        return fail(RAE_E_INVALID, "n_entities must be in [1, 2^31)");
+    if (a->nrows < 0) return fail(RAE_E_INVALID, "nrows must be >= 0");
+    if (a->row0 < 0 || a->row0 + a->nrows >= (1ll << 31))
+        return fail(RAE_E_INVALID, "row0 / nrows out of range");
+    if (!a->W) return fail(RAE_E_INVALID, "W is NULL");
+    if (!a->Wb) return fail(RAE_E_INVALID, "Wb is NULL");
+    if (!a->A) return fail(RAE_E_INVALID, "A is NULL");
+    if (!a->Ab) return fail(RAE_E_INVALID, "Ab is NULL");
+    if (a->decoder != RAE_DEC_RESCAL && (!a->C1 || !a->C2))
+        return fail(RAE_E_INVALID, "C1 / C2 is NULL");
+    if (bil && !a->R3) return fail(RAE_E_INVALID, "R3 is NULL");
+    if (!a->indptr || !a->indices) return fail(RAE_E_INVALID, "indptr / indices is NULL");
+    if (!a->args1 || !a->args2) return fail(RAE_E_INVALID, "args1 / args2 is NULL");
+    if (!a->neg1 || !a->neg2) return fail(RAE_E_INVALID, "neg1 / neg2 is NULL");
+    if (a->neg_stride < a->row0 + a->nrows)
+        return fail(RAE_E_INVALID, "neg_stride is smaller than row0 + nrows");
+    if (!a->sums_out) return fail(RAE_E_INVALID, "sums_out is NULL");
+    if (!a->workspace) return fail(RAE_E_INVALID, "workspace is NULL");
+    if ((uintptr_t)a->workspace & 255) return fail(RAE_E_INVALID, "workspace must be 256-byte aligned");
+    if (a->workspace_bytes < (int64_t)L.total)
+        return fail(RAE_E_INVALID, "workspace_bytes is smaller than rae_eval_workspace_bytes()");
+    if ((m % 4) == 0 && (((uintptr_t)a->W | (uintptr_t)a->Wb | (uintptr_t)a->C1 |
+                          (uintptr_t)a->C2 | (uintptr_t)a->R3) & 15))
+        return fail(RAE_E_INVALID, "W / Wb / C1 / C2 / R3 must be 16-byte aligned");
+    if ((r % 4) == 0 && ((uintptr_t)a->A & 15))
+        return fail(RAE_E_INVALID, "A must be 16-byte aligned");
+    return RAE_OK;
+}
+}  // namespace
+
+extern "C" int64_t rae_eval_workspace_bytes(const rae_eval_args* a) {
+    EvalLayout L;
+    if (eval_check(a, L, false)) return -1;
+    return (int64_t)L.total;
+}
+
+extern "C" int rae_eval_cost(const rae_eval_args* a, rae_stream_t stream) {
+    EvalLayout L;
+    const int rc = eval_check(a, L, true);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const int m = a->relations, r = a->embed;
+    const bool bil = a->decoder != RAE_DEC_SP, v4 = (m % 4) == 0;
+    char* ws = (char*)a->workspace;
+    double* partial = (double*)(ws + L.o_partial);
+    const size_t lds_dec = eval_dec_lds_floats(a->decoder, m, r) * 4;
+    const size_t lds_mt = eval_mt_lds_bytes(m);
+    // large dynamic LDS is opted into per kernel (not a stream operation)
+    if (lds_dec > 48 * 1024) {
+        HIPCHK(hipFuncSetAttribute(v4 ? (const void*)k_eval_dec<true> : (const void*)k_eval_dec<false>,
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_dec));
+    }
+    if (bil && lds_mt > 48 * 1024) {
+        HIPCHK(hipFuncSetAttribute(v4 ? (const void*)k_eval_mt<true> : (const void*)k_eval_mt<false>,
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_mt));
+    }
+    EvalArgs e;
+    e.dec = a->decoder; e.m = m; e.r = r; e.s = a->neg_samples; e.alpha = a->alpha;
+    e.W = a->W; e.Wb = a->Wb; e.A = a->A; e.Ab = a->Ab; e.C1 = a->C1; e.C2 = a->C2; e.R3 = a->R3;
+    e.indptr = a->indptr; e.indices = a->indices; e.values = a->values;
+    e.args1 = a->args1; e.args2 = a->args2; e.neg1 = a->neg1; e.neg2 = a->neg2;
+    e.neg_stride = a->neg_stride;
+    e.cap = (int)L.chunk; e.r4 = eval_r4(r);
+    e.P = (float*)(ws + L.o_P); e.vpart = (float*)(ws + L.o_v); e.wpart = (float*)(ws + L.o_w);
+    if (a->nrows == 0) {
+        hipLaunchKernelGGL(k_eval_acc, dim3(1), dim3(64), 0, st, partial, 0, a->sums_out, 1);
+        HIPCHK(hipGetLastError());
+        return RAE_OK;
+    }
+    for (int64_t c0 = 0; c0 < a->nrows; c0 += L.chunk) {
+        const int n = (int)std::min<int64_t>(L.chunk, a->nrows - c0);
+        e.row0 = a->row0 + c0;
+        e.n = n;
+        e.terms = a->terms_out ? a->terms_out + c0 * 3 : (float*)(ws + L.o_terms);
+        if (bil) {
+            const dim3 ge((unsigned)std::min(ceil_div(n, RAE_EV_NW), 65536));
+            const dim3 gm((unsigned)(eval_nbi(r) * eval_nbj(r)));
+            if (v4) {
+                hipLaunchKernelGGL(k_eval_enc<true>, ge, dim3(RAE_EV_BT), 0, st, e);
+                hipLaunchKernelGGL(k_eval_mt<true>, gm, dim3(RAE_EV_MTT), lds_mt, st, e);
+            } else {
+                hipLaunchKernelGGL(k_eval_enc<false>, ge, dim3(RAE_EV_BT), 0, st, e);
+                hipLaunchKernelGGL(k_eval_mt<false>, gm, dim3(RAE_EV_MTT), lds_mt, st, e);
+            }
+        }
+        const dim3 gd((unsigned)ceil_div(n, RAE_EV_TE));
+        if (v4) hipLaunchKernelGGL(k_eval_dec<true>, gd, dim3(RAE_EV_BT), lds_dec, st, e);
+        else hipLaunchKernelGGL(k_eval_dec<false>, gd, dim3(RAE_EV_BT), lds_dec, st, e);
+        const int nblk = ceil_div(n, RAE_EV_SUMROWS);
+        hipLaunchKernelGGL(k_eval_blocksum, dim3((unsigned)nblk), dim3(RAE_EV_BT), 0, st,
+                           (const float*)e.terms, n, partial);
+        hipLaunchKernelGGL(k_eval_acc, dim3(1), dim3(64), 0, st, (const double*)partial, nblk,
+                           a->sums_out, c0 == 0 ? 1 : 0);
+        HIPCHK(hipGetLastError());
+    }
     return RAE_OK;
 }

@@ -78,6 +78,7 @@ EXPORTS = (
     "rae_dp_unpack", "rae_dp_pack_at", "rae_dp_unpack_at",
     "rae_ipc_export", "rae_ipc_open", "rae_ipc_close", "rae_p2p_signals", "rae_set_peer",
     "rae_set_p2p_timeout", "rae_p2p_prologue",
+    "rae_eval_workspace_bytes", "rae_eval_cost",
 )
 RAE_IPC_HANDLE_BYTES = 64
 
@@ -121,6 +122,19 @@ class RaeBuffers(C.Structure):
         ("acc_C2", _P), ("acc_R3", _P),
         ("indptr", _P), ("indices", _P), ("values", _P), ("args1", _P), ("args2", _P),
         ("neg1", _P), ("neg2", _P), ("exchange", _P), ("costs", _P),
+    ]
+
+
+class RaeEvalArgs(C.Structure):
+    """rae_eval_args (include/rae.h): the forward-only objective's arguments."""
+    _fields_ = [
+        ("decoder", C.c_int32), ("relations", C.c_int32), ("embed", C.c_int32),
+        ("neg_samples", C.c_int32), ("n_entities", C.c_int64), ("alpha", C.c_float),
+        ("W", _P), ("Wb", _P), ("A", _P), ("Ab", _P), ("C1", _P), ("C2", _P), ("R3", _P),
+        ("indptr", _P), ("indices", _P), ("values", _P), ("args1", _P), ("args2", _P),
+        ("neg1", _P), ("neg2", _P), ("neg_stride", C.c_int64),
+        ("row0", C.c_int64), ("nrows", C.c_int64),
+        ("terms_out", _P), ("sums_out", _P), ("workspace", _P), ("workspace_bytes", C.c_int64),
     ]
 
 
@@ -193,6 +207,10 @@ def load(path: str | None = None):
     lib.rae_index_window.argtypes = [_P]
     lib.rae_index_window.restype = C.c_int64
     lib.rae_label.argtypes = [_P, _P, _P, _P, _P, C.c_int32, C.c_int64, C.c_int64, _P, _P, _P]
+    lib.rae_eval_workspace_bytes.argtypes = [C.POINTER(RaeEvalArgs)]
+    lib.rae_eval_workspace_bytes.restype = C.c_int64
+    lib.rae_eval_cost.argtypes = [C.POINTER(RaeEvalArgs), _P]
+    lib.rae_eval_cost.restype = C.c_int
     lib.rae_neg_sample.argtypes = [_P, C.c_int64, _P, C.c_int64, _P, _P]
     lib.rae_neg_sample_philox.argtypes = [_P, C.c_int64, C.c_uint64, C.c_uint64, C.c_int64, _P, _P]
     lib.rae_time_next.argtypes = [_P, _P, _P]

@@ -66,6 +66,11 @@ def get_command_args(argv=None, program_name="rae"):
     p.add_argument("--seed", type=int, default=2, help="a seed number")
     p.add_argument("--graph-chunk", type=int, default=64,
                    help="training steps captured per HIP graph (1 = eager launches)")
+    p.add_argument("--eval-cost", dest="eval_cost", action="store_true", default=False,
+                   help="after each epoch also report the forward-only objective of the "
+                        "evaluated splits (train, or valid and test)")
+    p.add_argument("--eval-seed", dest="eval_seed", type=int, default=None,
+                   help="key of the fixed negatives the objective is scored against")
     if argv is not None and len(argv) == 0:
         p.print_help()
         raise SystemExit(1)
@@ -119,7 +124,8 @@ def main(argv=None):
                              args.embed_size, args.relations, args.neg_samples, args.l1, args.l2,
                              args.optimizer, args.model_name, args.decoder, args.ext_emb,
                              args.ext_reg, args.freq_eval, args.alpha, device=dev, world_size=ws,
-                             rank=rk, exchange=exchange, graph_chunk=args.graph_chunk)
+                             rank=rk, exchange=exchange, graph_chunk=args.graph_chunk,
+                             eval_cost=args.eval_cost, eval_seed=args.eval_seed)
     if exchange is not None:
         ind.compile_function()
         rdist.warm_up(exchange, ind.engine.exchange_buf)

@@ -15,6 +15,7 @@ and the update kernels, so every rank applies the identical update.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 import socket
@@ -27,6 +28,10 @@ from .data import batch_nnz_stats
 
 
 _hip = None
+
+# TrainEngine.evaluate's result: cost = reconstruction + entropy (Python floats), the
+# (nrows, 3) terms tensor (or None) and the three double column sums (S_pos, S_H, S_neg)
+EvalResult = collections.namedtuple("EvalResult", "cost reconstruction entropy terms sums")
 
 
 def _upload_graph(g, stream):
@@ -787,3 +792,118 @@ class TrainEngine:
             C.c_void_p(lab.data_ptr()), C.c_void_p(pr.data_ptr()) if pr is not None else None,
             self._stream()), "rae_label")
         return lab, pr
+
+    # ------------------------------------------------------------------ held-out objective
+    EVAL_SEED = 0x5EEDE7A1           # Philox key of the evaluation negatives (not the model's RNG)
+
+    def eval_negatives(self, split: DeviceSplit, sampler=None, seed: int | None = None):
+        """Two (s, N_split) int32 device arrays of negatives for scoring `split`, drawn over
+        negSamplingCum with rae_neg_sample_philox at a fixed key (neg1 at counter offset 0, neg2
+        at s * N_split) and cached per split: every epoch scores against the same negatives.
+        Never touches the model's RandomState (only sampler.cum is read)."""
+        seed = self.EVAL_SEED if seed is None else int(seed)
+        cache = self.__dict__.setdefault("_eval_negs", {})
+        hit = cache.get(id(split))
+        if hit is not None and hit[0] is split and hit[1] == seed:
+            return hit[2], hit[3]
+        sampler = sampler if sampler is not None else getattr(self, "eval_sampler", None)
+        if getattr(self, "_cum_dev", None) is None:
+            if sampler is None:
+                raise ValueError("eval_negatives needs a sampler (its negSamplingCum)")
+            self._cum_dev = torch.as_tensor(np.asarray(sampler.cum, dtype=np.float64),
+                                            device=self.device)
+        count = self.s * split.N
+        out = []
+        for which in range(2):
+            buf = torch.empty((self.s, split.N), dtype=torch.int32, device=self.device)
+            if count:
+                _lib.check(self.lib.rae_neg_sample_philox(
+                    C.c_void_p(self._cum_dev.data_ptr()), int(self._cum_dev.numel()), seed,
+                    which * count, count, C.c_void_p(buf.data_ptr()), self._stream()),
+                    "rae_neg_sample_philox")
+            out.append(buf)
+        cache[id(split)] = (split, seed, out[0], out[1])
+        return out[0], out[1]
+
+    def _eval_neg_arg(self, neg):
+        if torch.is_tensor(neg):
+            t = neg.to(device=self.device, dtype=torch.int32)
+        else:
+            t = torch.as_tensor(np.ascontiguousarray(neg, dtype=np.int32), device=self.device)
+        t = t.contiguous()
+        if t.dim() != 2 or t.shape[0] != self.s:
+            raise ValueError(f"negatives must be ({self.s}, columns), got {tuple(t.shape)}")
+        return t
+
+    def evaluate(self, split: DeviceSplit, row0: int = 0, nrows: int | None = None, neg1=None,
+                 neg2=None, seed: int | None = None, terms: bool = False,
+                 neg_per_call: bool = False):
+        """The forward-only objective (rae_eval_cost) of rows [row0, row0+nrows) of `split` at
+        the current parameters: EvalResult(cost, reconstruction, entropy, terms, sums) with
+        cost = reconstruction + entropy = -(S_pos + S_neg)/D - 2 S_H/D, D = nrows (4 + 2s) --
+        the data term func['train'] returns, without the L1 / L2 regularisers; Python floats
+        from the double sums.  terms=True: also the (nrows, 3) fp32 tensor (pos, H, neg).
+        neg1 / neg2: (s, >= row0+nrows) arrays whose column is the row within the split
+        (default: eval_negatives(split)); neg_per_call: (s, nrows) arrays whose column is the
+        example within the range (func['train']'s convention).  Touches no parameter,
+        accumulator, plan state, cursor, row index, training negative or prefetch, and not the
+        model's RNG.  Partitioned update with stale rows: gathers the parameters first (a
+        collective, like label)."""
+        if self.stale(accumulators=False):
+            self.sync_replicas(accumulators=False)
+        row0 = int(row0)
+        nrows = split.N - row0 if nrows is None else int(nrows)
+        if row0 < 0 or nrows < 0 or row0 + nrows > split.N:
+            raise IndexError(f"rows [{row0}, {row0 + nrows}) out of the split's {split.N}")
+        if (neg1 is None) != (neg2 is None):
+            raise ValueError("give both neg1 and neg2 or neither")
+        if neg1 is None:
+            n1, n2 = self.eval_negatives(split, seed=seed)
+        else:
+            n1, n2 = self._eval_neg_arg(neg1), self._eval_neg_arg(neg2)
+        if n1.shape != n2.shape:
+            raise ValueError("neg1 and neg2 differ in shape")
+        shift = row0 if neg_per_call else 0     # the range as rows [0, nrows) of a shifted view
+        if n1.shape[1] < row0 - shift + nrows:
+            raise ValueError(f"negatives have {n1.shape[1]} columns, rows need "
+                             f"{row0 - shift + nrows}")
+        out = torch.empty((nrows, 3), dtype=torch.float32, device=self.device) if terms else None
+        self.queue_evaluate(split, row0 - shift, nrows, n1, n2, out, shift)
+        sp_, sh_, sn_ = (float(x) for x in self._eval_sums.cpu().numpy())
+        D = float(nrows * (4 + 2 * self.s))
+        rec = -(sp_ + sn_) / D if nrows else 0.0
+        ent = -2.0 * sh_ / D if nrows else 0.0
+        return EvalResult(rec + ent, rec, ent, out, (sp_, sh_, sn_))
+
+    def queue_evaluate(self, split: DeviceSplit, row0: int, nrows: int, n1, n2, out=None,
+                       shift: int = 0):
+        """Queue rae_eval_cost on the current stream (no host synchronisation): rows
+        [row0, row0+nrows) of `split` viewed from row `shift` on, negatives n1 / n2 (device int32,
+        (s, stride)), terms into `out` ((nrows, 3) fp32 or None), the sums into self._eval_sums.
+        evaluate() is this plus the read-back; tools/eval_bench.py times it alone."""
+        named = self._named
+        R3 = named.get("R", named.get("C"))
+        a = _lib.RaeEvalArgs()
+        a.decoder = self.cfg.decoder
+        a.relations, a.embed, a.neg_samples = self.m, self.r, self.s
+        a.n_entities = self.cfg.n_entities
+        a.alpha = self.cfg.alpha
+        p = _lib.ptr
+        a.W, a.Wb, a.A, a.Ab = p(named["W"]), p(named["Wb"]), p(named["A"]), p(named["Ab"])
+        a.C1, a.C2, a.R3 = p(named.get("C1")), p(named.get("C2")), p(R3)
+        a.indptr = split.indptr.data_ptr() + 4 * shift
+        a.indices, a.values = p(split.indices), p(split.values)
+        a.args1 = split.args1.data_ptr() + 4 * shift
+        a.args2 = split.args2.data_ptr() + 4 * shift
+        a.neg1, a.neg2, a.neg_stride = p(n1), p(n2), int(n1.shape[1])
+        a.row0, a.nrows = int(row0), int(nrows)
+        if getattr(self, "_eval_ws", None) is None:      # once per engine
+            need = int(self.lib.rae_eval_workspace_bytes(C.byref(a)))
+            if need < 0:
+                _lib.check(-1, "rae_eval_workspace_bytes")
+            self._eval_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+            self._eval_sums = torch.zeros(3, dtype=torch.float64, device=self.device)
+        a.terms_out = p(out)
+        a.sums_out = p(self._eval_sums)
+        a.workspace, a.workspace_bytes = p(self._eval_ws), int(self._eval_ws.numel())
+        _lib.check(self.lib.rae_eval_cost(C.byref(a), self._stream()), "rae_eval_cost")

@@ -48,6 +48,24 @@ class _LabelFunction:
         return lab.cpu().numpy()
 
 
+class _CostFunction:
+    """``func['cost_<split>'](batch_index, neg1, neg2) -> cost``: func['train']'s signature and
+    batch slicing (rows [b*l, (b+1)*l), (s, l) negatives) without the update -- the data term
+    of the cost (no L1 / L2), by rae_eval_cost (TrainEngine.evaluate)."""
+
+    def __init__(self, engine, split, batch_size):
+        self.engine = engine
+        self.split = split
+        self.l = batch_size
+
+    def __call__(self, batch_index, neg1, neg2):
+        b = int(batch_index)
+        if not 0 <= b < self.split.N // self.l:
+            raise IndexError(f"batch index {b} out of range [0, {self.split.N // self.l})")
+        return self.engine.evaluate(self.split, b * self.l, self.l, neg1, neg2,
+                                    neg_per_call=True).cost
+
+
 class ReconstructInducer:
     def __init__(self, data, gold_standard, rng, nb_epochs, learning_rate, batch_size,
                  embed_size, nb_relations, nb_neg_samples, lambda1, lambda2, optimization,
@@ -55,7 +73,8 @@ class ReconstructInducer:
                  frequent_eval, alpha, *, device=None, world_size=1, rank=0, exchange=None,
                  graph_chunk=64, neg_sampler="device", neg_seed=0, mfma_bf16=False,
                  kernel_forms=None, dp_update="replicated", index_window=0,
-                 index_overlap=True, p2p_cross_device=False, p2p_timeout=5.0):
+                 index_overlap=True, p2p_cross_device=False, p2p_timeout=5.0,
+                 eval_cost=False, eval_seed=None):
         self.data = data
         self.goldStandard = gold_standard
         self.rng = rng
@@ -92,6 +111,12 @@ class ReconstructInducer:
         # when asked for (engine.TrainEngine._p2p_setup); a wait's bound in seconds
         self.p2p_cross_device = bool(p2p_cross_device)
         self.p2p_timeout = float(p2p_timeout)
+        # eval_cost: learn() also reports the forward-only objective of the splits it evaluates
+        # after each epoch, against negatives fixed by eval_seed (TrainEngine.eval_negatives;
+        # every rank scores the whole split)
+        self.eval_cost = bool(eval_cost)
+        self.eval_seed = eval_seed
+        self.eval_costs = {s: [] for s in SPLIT_LABELS}
         self.negativeSampler = NegativeExampleGenerator(rng, data.negSamplingCum)   # :85
         self.modelID = (f"{decoder_model}_{model_name}_maxepoch{nb_epochs}_lr{learning_rate}"
                         f"_embedsize{embed_size}_l1{lambda1}_l2{lambda2}_opt{optimization}"
@@ -129,6 +154,7 @@ class ReconstructInducer:
         self.cur_epoch = 0
         self.train_errors = []
         self.epoch_costs = []
+        self.eval_costs = {s: [] for s in SPLIT_LABELS}
         self.modelFunc = OieModelFunctions(self.rng, self.embedSize, self.relationNum,
                                            self.neg_sample_num, self.batch_size,
                                            self.decoder_type, self.data, self.extendedReg,
@@ -160,9 +186,13 @@ class ReconstructInducer:
                                   p2p_cross_device=self.p2p_cross_device,
                                   p2p_timeout=self.p2p_timeout)
         self.func["train"] = _TrainFunction(self.engine)
+        self.engine.eval_sampler = self.negativeSampler      # its CDF only (eval_negatives)
+        self._dev_split = {}
         for key in self.data.generate_split_keys():
             ds = self.engine.split if key == "train" else DeviceSplit(self.data.split[key], self.device)
+            self._dev_split[key] = ds
             self.func["label_" + key] = _LabelFunction(self.engine, ds, self.batch_size)
+            self.func["cost_" + key] = _CostFunction(self.engine, ds, self.batch_size)
 
     def _check_for_compiled_functions(self):
         return self.func.get("train") is not None
@@ -243,7 +273,22 @@ class ReconstructInducer:
                 for split in SPLIT_LABELS[1:]:
                     self.cluster[split] = self.get_clusters_sets(split)
                     self._evaluate(split, verbose=verbose)
+            if self.eval_cost:
+                for split in (SPLIT_LABELS[:1] if self._mode() == 1 else SPLIT_LABELS[1:]):
+                    self.evaluate_cost(split, verbose=verbose)
         return self.train_errors
+
+    def evaluate_cost(self, split, verbose=True):
+        """The forward-only objective of the whole `split` at the current parameters, against
+        the split's fixed evaluation negatives (eval_seed); appended to eval_costs[split]."""
+        if not self._check_for_compiled_functions():
+            self.compile_function()
+        res = self.engine.evaluate(self._dev_split[split], seed=self.eval_seed)
+        self.eval_costs[split].append(res.cost)
+        if verbose:
+            print("{} objective: {:.6f} (reconstruction {:.6f}, entropy {:.6f})".format(
+                split, res.cost, res.reconstruction, res.entropy))
+        return res
 
     # ------------------------------------------------------------------ clusters / eval
     def _labels(self, split):
