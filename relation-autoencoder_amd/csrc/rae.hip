@@ -21,6 +21,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <type_traits>
 
 #include "../../include/rae.h"
 #include "rae_bilinear.hpp"
@@ -35,6 +36,7 @@
 #include "rae_sp.hpp"
 #include "rae_step.hpp"
 #include "rae_update.hpp"
+#include "rae_plan.hpp"
 
 using namespace rae;
 
@@ -132,8 +134,6 @@ __global__ __launch_bounds__((dp2_threads<NJS, MT>())) void k_bil_dp2(StepArgs a
 }
 __global__ __launch_bounds__(RAE_BT) void k_bil_prep(StepArgs a) { bil_prep(a); }
 // the R-tensor update: one wave per 16 rows (i, j) of R x all m relations (slot nCt + tile)
-__host__ __device__ inline int n_ctiles(int dec, int r, int m);
-__host__ __device__ inline int n_rtiles(int dec, int r, int m);
 template <int OPT, bool LDS>
 __global__ __launch_bounds__(RAE_BT) void k_bil_rows(StepArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -215,13 +215,6 @@ __global__ __launch_bounds__(RAE_BT) void k_dp_move(StepArgs a) {
     dp_move<PACK>(a, t, threadIdx.x & 63);
 }
 
-__host__ __device__ inline int n_ctiles(int dec, int r, int m) {
-    return dec != RAE_DEC_RESCAL ? 2 * ((r + 15) / 16) * ((m + 15) / 16) : 0;
-}
-__host__ __device__ inline int n_rtiles(int dec, int r, int m) {
-    return dec != RAE_DEC_SP ? (r * r + 15) / 16 : 0;    // 16 rows of R/C x all m each
-}
-
 #ifdef RAE_STAMPS
 #define RAE_WAVE_END()                                                                      \
     do {                                                                                    \
@@ -232,65 +225,12 @@ __host__ __device__ inline int n_rtiles(int dec, int r, int m) {
 #define RAE_WAVE_END() do { } while (0)
 #endif
 
-// Update launch layout (workgroups of RAE_NWAVE = 4 waves), in dispatch order:
-//   [0, nT)              one dense 16x16 tile per workgroup: C1/C2 tiles, then Wb tiles
-//                        (no row index needed: they start at once; K = batch split 4 ways)
-//   [nT, nT + nP)        one wave task each, no row index needed: the cost
-//   then, after the batch's index header: one workgroup per very heavy A row, per very heavy
-//   W row, and the remaining workgroups' waves grid-stride over the heavy A rows, heavy W
-//   rows, light A rows, light W rows (one row per wave)
-__host__ __device__ inline int update_wave_free_tasks(int dec, int r, int m) {
-    return 1;                                            // the cost (R rows: k_bil_rows)
-}
-#ifndef RAE_SPLIT_RM
-#define RAE_SPLIT_RM 32768    // r*m above which the SP forward runs split (rae_sp_split.hpp)
-#endif
 #ifndef RAE_ROWS_FIRST
 #define RAE_ROWS_FIRST 0      // update: dispatch the row tasks ahead of the dense tiles
-#endif
-#ifndef RAE_ROWPCT
-#define RAE_ROWPCT 100        // row-task waves per 100 dispatch-table capacity entries
-#endif
-#ifndef RAE_HCH
-#define RAE_HCH 128           // very heavy rows above this many records are split into chunks
-#endif
-#ifndef RAE_PRIV_MAXL
-#define RAE_PRIV_MAXL 4096    // private rows (auto) below this global batch (equal at 4096)
-#endif
-#ifndef RAE_HCH_MINL
-#define RAE_HCH_MINL 2048     // ... in plans with a global batch of at least this many examples
-#endif
-#ifndef RAE_NVC_MIN
-#define RAE_NVC_MIN 32
-#endif
-#ifndef RAE_NVC_DIV
-#define RAE_NVC_DIV 2         // very heavy row workgroup slots: max(32, L / RAE_NVC_DIV)
-#endif
-#ifndef RAE_UPD_WGCAP
-#define RAE_UPD_WGCAP 6144    // row-task workgroups (grid-stride beyond; 1536 = one resident round)
 #endif
 #ifndef RAE_PRIV_LAST
 #define RAE_PRIV_LAST 1       // private-row workgroups dispatched after every other update task
 #endif
-#ifndef RAE_PRIV_ROWW
-#define RAE_PRIV_ROWW 4       // private rows: row-task waves per example of the global batch
-#endif
-// own: the share of the global batch's rows this rank updates (1 / G for the partitioned
-// data-parallel update: the row grid and the very heavy slots are sized from it)
-__host__ __device__ inline int64_t update_grid(int dec, int r, int m, int TC, int NVC, int L,
-                                               int priv, int privc, int own) {
-    const int nT = n_ctiles(dec, r, m) + (m + 15) / 16;
-    const int nP = (update_wave_free_tasks(dec, r, m) + RAE_NWAVE - 1) / RAE_NWAVE;
-    int64_t rows = ((int64_t)TC * RAE_ROWPCT / 100 / own + RAE_NWAVE - 1) / RAE_NWAVE;
-    // with the private rows (StepArgs::priv) taken per example by leading workgroups, the
-    // dispatch table keeps ~5 % of the rows: a smaller row grid, grid-striding when a batch has more
-    if (priv) {
-        const int64_t pr = ((int64_t)L * RAE_PRIV_ROWW / own + RAE_NWAVE - 1) / RAE_NWAVE;
-        if (pr < rows) rows = pr;
-    }
-    if (RAE_UPD_WGCAP > 0 && rows > RAE_UPD_WGCAP) rows = RAE_UPD_WGCAP;
-    return (int64_t)nT + nP + NVC + rows + (priv ? (int64_t)priv_workgroups(privc, L) : 0);
-}
 
 // LDS of one update workgroup: workgroup tasks' partials (a row: Q vectors per lane, or a tile:
 // 4 floats per lane, per wave) + the Ab partials
@@ -633,34 +573,17 @@ static int fail(int code, const std::string& msg) {
             return fail(RAE_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_));       \
     } while (0)
 
-struct rae_plan {
+// the resolved spec (rae_plan.hpp: args, forms, geometry, workspace layout) + what creation
+// and the calls after it add
+struct rae_plan : PlanSpec {
     rae_config cfg;
     rae_buffers buf;
-    StepArgs args;
-    int64_t* d_cursor = nullptr;
     int64_t cursor_moves = 0;  // host count of rae_set_cursor / rae_advance_cursor calls
-    int64_t* d_zero = nullptr;
-    int* d_err = nullptr;
     int* h_err = nullptr;   // pinned host word of rae_check_on
     unsigned* d_sig = nullptr;  // peer-to-peer signal counters (own allocation: IPC-exported)
     bool peers_set = false;     // rae_set_peer called for every other rank
     int peers_mask = 0;
     char* ws = nullptr;
-    size_t smem_fwd = 0;
-    size_t smem_idx = 0;    // k_idx_sort<true> (partitions of more than RAE_IDX_FAST keys)
-    size_t smem_idxf = 0;   // k_idx_sort<false>
-    size_t smem_dec = 0;
-    size_t smem_mt = 0;     // k_bil_mt: one 8 x 16 x m block of R in LDS
-    size_t smem_mt0 = 0;    // ... its first pass (no transposed image for dP): less LDS per WG
-    bool mt_direct = false; // fp32 blocks beyond LDS (m > 320): k_bil_mt reads R from L2
-    bool sp_split = false;  // SP forward as enc -> GEMM -> dec -> GEMM -> fin (large shapes)
-    size_t smem_spe = 0;    // k_sp_enc
-    size_t smem_spd = 0;    // k_sp_dec (one negative side)
-    bool mt_bf16 = false;
-    int grid_fwd = 0, grid_update = 0, grid_dense = 0;
-    bool v4 = false;
-    int q = 1;
-    int dp2 = 0;            // bf16 dP kernel: 0 none (bil_gemm_dp*), 1 k_bil_dp2<7,7>, 2 <8,8>
     unsigned long long* stamps_fwd = nullptr;
     unsigned long long* stamps_upd = nullptr;
     hipEvent_t t_start = nullptr, t_stop = nullptr;   // armed by rae_time_next for ONE call
@@ -681,6 +604,22 @@ struct rae_plan {
         }                                                                                 \
     } while (0)
 
+// compile-time dispatch: f gets the runtime value as a std::integral_constant (RAE_CV reads it).
+// Kernels are instantiated in the order the launch code first names them (true / 1 / AdaGrad
+// first), and the device code follows that order down to the inliner's choices: a change of
+// the nesting below is a change of the code object (compare the disassembly).
+#define RAE_CV(x) decltype(x)::value
+template <class F> static void with_bool(bool b, F&& f) {
+    if (b) f(std::true_type{}); else f(std::false_type{});
+}
+template <class F> static void with_q(int q, F&& f) {          // row slots per lane: 1 or 2
+    if (q == 1) f(std::integral_constant<int, 1>{}); else f(std::integral_constant<int, 2>{});
+}
+template <class F> static void with_opt(int opt, F&& f) {      // RAE_OPT_ADAGRAD 0 / RAE_OPT_SGD 1
+    if (opt == RAE_OPT_ADAGRAD) f(std::integral_constant<int, 0>{});
+    else f(std::integral_constant<int, 1>{});
+}
+
 extern "C" const char* rae_last_error(void) { return g_last_error.c_str(); }
 extern "C" int rae_version(void) { return RAE_VERSION; }
 #ifndef RAE_BUILD_ID
@@ -696,464 +635,83 @@ extern "C" int rae_version(void) { return RAE_VERSION; }
 __attribute__((used)) static const char g_build_id[] = "RAE_BUILD_ID:" RAE_BUILD_KIND RAE_BUILD_ID;
 extern "C" const char* rae_build_id(void) { return g_build_id + 13; }
 
-// the SP decoder exchanges wire records between ranks (rae_step.hpp): V1 / V2 / G1 are
-// recomputed after the all-gather instead of crossing xGMI (1); with dense partials (2) the
-// records carry each rank's partial dC1 / dC2 / dWb block instead of every example's dw1 / dw2
-static int wire_records(const rae_config& c) {
-    if (c.decoder != RAE_DEC_SP || c.world_size <= 1) return 0;
-    if (c.dp_dense == RAE_DPDENSE_RECORDS) return 1;
-    if (c.dp_dense == RAE_DPDENSE_PARTIALS) return 2;
-    // partials when their chunk is at most half of dw1 / dw2 (l >~ 2 m): below that they move
-    // about as many bytes and k_dpart (~4 us at C3, l = 100) sits on the critical path
-    const int pc = align4((dense_partial_floats(c.embed, c.relations) + c.batch_size - 1) /
-                          c.batch_size);
-    return pc <= align4(c.embed) ? 2 : 1;
-}
 extern "C" int64_t rae_exchange_record_floats(const rae_config* cfg) {
     if (!cfg) return -1;
-    return make_layout(cfg->decoder, cfg->relations, cfg->embed, cfg->neg_samples,
-                       wire_records(*cfg), cfg->batch_size).rec;
+    return plan_layout(*cfg).rec;
 }
 extern "C" int64_t rae_exchange_floats(const rae_config* cfg) {
     if (!cfg) return -1;
     return rae_exchange_record_floats(cfg) * (int64_t)cfg->batch_size * cfg->world_size;
 }
 
-static int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+// large dynamic LDS is opted into per kernel
+static void plan_set_kernel_attributes(const rae_plan* p) {
+    auto lds = [](const void* f, size_t bytes) {
+        (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    };
+    const void* fwd[] = {(const void*)k_forward<true, DimsC3>, (const void*)k_forward<false, DimsC2>,
+                         (const void*)k_forward<true, DynDims>, (const void*)k_forward<false, DynDims>,
+                         (const void*)k_bil_enc<true>, (const void*)k_bil_enc<false>,
+                         (const void*)k_bil_enc_fast<DimsC3>,
+                         (const void*)k_sp_dec<true>, (const void*)k_sp_dec<false>};
+    for (const void* f : fwd) lds(f, p->smem_fwd);
+    if (p->sp_split) {
+        lds((const void*)k_sp_enc<true>, p->smem_spe);
+        lds((const void*)k_sp_enc<false>, p->smem_spe);
+    }
+    if (p->cfg.decoder != RAE_DEC_SP) {
+        lds((const void*)k_bil_dp2<7, 7>, dp2_lds_bytes<7, 7>());
+        lds((const void*)k_bil_dp2<8, 8>, dp2_lds_bytes<8, 8>());
+        lds((const void*)k_bil_mt<true>, p->smem_mt);
+        lds((const void*)k_bil_mt<true, false, false>, p->smem_mt);
+        lds((const void*)k_bil_mt<false>, p->smem_mt);
+        lds((const void*)k_bil_dec<true>, p->smem_dec);
+        lds((const void*)k_bil_dec<false>, p->smem_dec);
+    }
+    lds((const void*)k_idx_sort<true>, p->smem_idx);
+    lds((const void*)k_build_dplists, 4 * RAE_DPL_KEYS + 4 * 32);
+}
 
+// resolve (rae_plan.hpp: every check, form and the workspace layout; nothing is allocated for a
+// config that is rejected) -> allocate -> bind -> kernel attributes.  A failure after the plan
+// exists leaves through rae_plan_destroy.
 extern "C" int rae_plan_create(const rae_config* cfg, const rae_buffers* buf, rae_plan** out) {
     if (!cfg || !buf || !out) return fail(RAE_E_INVALID, "null argument");
-    const rae_config& c = *cfg;
-    if (c.decoder < 0 || c.decoder > 2) return fail(RAE_E_INVALID, "decoder must be 0..2");
-    if (c.optimizer < 0 || c.optimizer > 1) return fail(RAE_E_INVALID, "optimizer must be 0..1");
-    if (c.relations < 1 || c.relations > 1024)
-        return fail(RAE_E_INVALID, "relations must be in [1, 1024]");
-    if (c.embed < 1 || c.embed > 1024) return fail(RAE_E_INVALID, "embed must be in [1, 1024]");
-    if (c.neg_samples < 1) return fail(RAE_E_INVALID, "neg_samples must be >= 1");
-    if (c.sp_forward < RAE_SPFWD_AUTO || c.sp_forward > RAE_SPFWD_SPLIT ||
-        c.bil_dp < RAE_BILDP_AUTO || c.bil_dp > RAE_BILDP_MTILE ||
-        c.bil_prep < RAE_BILPREP_AUTO || c.bil_prep > RAE_BILPREP_KERNEL ||
-        c.dp_update < RAE_DPUPD_REPLICATED || c.dp_update > RAE_DPUPD_PARTITIONED ||
-        c.priv_rows < RAE_PRIV_AUTO || c.priv_rows > RAE_PRIV_ON ||
-        c.dp_dense < RAE_DPDENSE_AUTO || c.dp_dense > RAE_DPDENSE_PARTIALS ||
-        c.heavy_chunk < RAE_HCHUNK_AUTO || c.heavy_chunk > RAE_HCHUNK_ON ||
-        c.dp_xchg < RAE_XCHG_COLLECTIVE || c.dp_xchg > RAE_XCHG_P2P_PIPE)
-        return fail(RAE_E_INVALID, "unknown kernel form (sp_forward / bil_dp / bil_prep / dp_update / "
-                                   "priv_rows / dp_dense / heavy_chunk / dp_xchg)");
-    if (c.dp_xchg != RAE_XCHG_COLLECTIVE &&
-        (c.dp_update != RAE_DPUPD_PARTITIONED || c.world_size > 31 || c.embed % 4 ||
-         c.relations % 4 || c.embed > 512 || c.relations > 512))
-        return fail(RAE_E_INVALID, "the peer-to-peer exchange runs the partitioned update "
-                                   "(world_size <= 31; embed and relations multiples of 4, <= 512)");
-    // the pipelined form marks a row's reading peers in one byte, and its update pushes rows
-    // from the row tasks only (not from the private-row tasks)
-    if (c.dp_xchg == RAE_XCHG_P2P_PIPE && (c.world_size > 8 || c.priv_rows == RAE_PRIV_ON))
-        return fail(RAE_E_INVALID, "the pipelined peer-to-peer exchange needs world_size <= 8 and "
-                                   "private rows off");
-    if (c.bil_dp == RAE_BILDP_MTILE && !(c.decoder != RAE_DEC_SP && c.mfma_bf16 && c.relations <= 128))
-        return fail(RAE_E_INVALID, "bil_dp MTILE needs a bf16 bilinear plan with relations <= 128");
-    if (c.dp_update == RAE_DPUPD_PARTITIONED && (c.lambda1 != 0.f || c.lambda2 != 0.f))
-        return fail(RAE_E_INVALID, "the partitioned data-parallel update needs lambda1 = lambda2 = 0 "
-                                   "(a regulariser makes every W row change every step)");
-    if (c.batch_size < 1 || c.world_size < 1 || c.rank < 0 || c.rank >= c.world_size)
-        return fail(RAE_E_INVALID, "bad batch_size/world_size/rank");
-    if (c.n_examples < (int64_t)c.batch_size * c.world_size)
-        return fail(RAE_E_INVALID, "fewer examples than one global batch");
-    if (c.n_entities < 1 || c.n_features < 1 || c.n_entities >= (1ll << 31))
-        return fail(RAE_E_INVALID, "bad n_entities / n_features");
-    if (!buf->W || !buf->Wb || !buf->A || !buf->Ab || !buf->indptr || !buf->indices ||
-        !buf->args1 || !buf->args2 || !buf->exchange || !buf->costs)
-        return fail(RAE_E_INVALID, "missing required buffer");
-    if (c.decoder != RAE_DEC_RESCAL && (!buf->C1 || !buf->C2))
-        return fail(RAE_E_INVALID, "C1/C2 required for this decoder");
-    if (c.decoder != RAE_DEC_SP && !buf->R3) return fail(RAE_E_INVALID, "R/C tensor required");
-    if (c.optimizer == RAE_OPT_ADAGRAD &&
-        (!buf->acc_W || !buf->acc_Wb || !buf->acc_A || !buf->acc_Ab ||
-         (c.decoder != RAE_DEC_RESCAL && (!buf->acc_C1 || !buf->acc_C2)) ||
-         (c.decoder != RAE_DEC_SP && !buf->acc_R3)))
-        return fail(RAE_E_INVALID, "AdaGrad accumulators required");
-
-    {
-        const RecLayout lay = make_layout(c.decoder, c.relations, c.embed, c.neg_samples,
-                                          wire_records(c), c.batch_size);
-        if ((int64_t)lay.rec * c.batch_size * c.world_size >= (1ll << 31) ||
-            (int64_t)3 * align4(c.embed) * c.batch_size * c.world_size >= (1ll << 31))
-            return fail(RAE_E_INVALID, "exchange buffer exceeds 2^31 floats (global batch too large)");
-    }
+    PlanSpec spec;
+    std::string err;
+    if (const int rc = plan_resolve(*cfg, *buf, spec, err)) return fail(rc, err);
     rae_plan* p = new rae_plan();
-    p->cfg = c;
+    static_cast<PlanSpec&>(*p) = spec;
+    p->cfg = *cfg;
     p->buf = *buf;
-    StepArgs& a = p->args;
-    memset(&a, 0, sizeof(a));
-    const int L = c.batch_size * c.world_size;
-    const int NJ = 2 + 2 * c.neg_samples;
-    a.dec = c.decoder;
-    a.opt = c.optimizer;
-    a.N = c.n_examples;
-    a.d = c.n_features;
-    a.n = c.n_entities;
-    a.m = c.relations;
-    a.r = c.embed;
-    a.s = c.neg_samples;
-    a.l = c.batch_size;
-    a.L = L;
-    a.rank = c.rank;
-    a.lr = c.learning_rate;
-    a.alpha = c.alpha;
-    // adjust = batch / N_train (learning/OieInduction.py:131) with the GLOBAL batch
-    const double adjust = (double)L / (double)c.n_examples;
-    a.l1adj = (float)(c.lambda1 * adjust);
-    a.l2adj = (float)(c.lambda2 * adjust);
-    a.invD = (float)(1.0 / (4.0 * L + 2.0 * L * c.neg_samples));
-    a.ext_reg = c.ext_reg;
-    a.reg_on = (c.lambda1 != 0.f || c.lambda2 != 0.f) ? 1 : 0;
-    a.indptr = buf->indptr;
-    a.indices = buf->indices;
-    a.values = buf->values;
-    a.args1 = buf->args1;
-    a.args2 = buf->args2;
-    a.neg1 = buf->neg1;
-    a.neg2 = buf->neg2;
-    a.neg_mode = c.neg_mode;
-    a.neg_stride = c.neg_stride;
-    a.W = buf->W; a.Wb = buf->Wb; a.A = buf->A; a.Ab = buf->Ab;
-    a.C1 = buf->C1; a.C2 = buf->C2; a.R3 = buf->R3;
-    a.aW = buf->acc_W; a.aWb = buf->acc_Wb; a.aA = buf->acc_A; a.aAb = buf->acc_Ab;
-    a.aC1 = buf->acc_C1; a.aC2 = buf->acc_C2; a.aR3 = buf->acc_R3;
-    a.ex = buf->exchange;
-    a.lay = make_layout(c.decoder, c.relations, c.embed, c.neg_samples, wire_records(c),
-                        c.batch_size);
-    // the update's record vectors: in the records, or (wire record) the vector buffer
-    a.vb = a.ex;
-    a.vbs = a.lay.rec;
-    a.vG1 = a.lay.oG1; a.vV1 = a.lay.oV1; a.vV2 = a.lay.oV2; a.vG2 = a.lay.oG2;
-    if (a.lay.wire) {
-        const int r4 = align4(c.embed);
-        a.vbs = 3 * r4;
-        a.vV1 = 0; a.vV2 = r4; a.vG1 = 2 * r4; a.vG2 = 0;
-    }
-    // the forward's dw1 / dw2: in the records, or (dense partials) a rank-local buffer
-    a.dpart = a.lay.wire == 2 ? 1 : 0;
-    a.dwb = a.ex;
-    a.dws = a.lay.rec;
-    a.dw1o = a.lay.odw1; a.dw2o = a.lay.odw2;
-    if (a.dpart) {
-        a.dws = 2 * align4(c.embed);
-        a.dw1o = 0; a.dw2o = align4(c.embed);
-    }
-    a.costs = buf->costs;
-    p->v4 = (c.relations % 4 == 0) && (c.embed % 4 == 0);
-    {
-        const int vw = p->v4 ? 4 : 1;
-        const int qa = ceil_div(c.embed / vw, 64), qm = ceil_div(c.relations / vw, 64);
-        const int q = qa > qm ? qa : qm;
-        if (q > 2) {
-            delete p;
-            return fail(RAE_E_INVALID,
-                        "relations/embed are limited to 512 (128 when not multiples of 4)");
-        }
-        p->q = q <= 1 ? 1 : 2;
-    }
-
-    // row-index partitions: ~1024 records per partition on average, LDS holds RAE_KCAP
-    a.RA = L * NJ;
-    a.RW = c.max_batch_nnz > 0 ? c.max_batch_nnz : 1;
-    a.HA = index_partitions(a.RA);
-    a.HW = index_partitions(a.RW);
-    a.G = c.world_size;
-    a.part = c.dp_update == RAE_DPUPD_PARTITIONED ? 1 : 0;
-    if (a.HA > RAE_IDX_HMAX || a.HW > RAE_IDX_HMAX) {
-        delete p;
-        return fail(RAE_E_INVALID, "global batch too large for the row index (more than " +
-                                   std::to_string(RAE_IDX_HMAX * RAE_IDX_PART) +
-                                   " records of one table)");
-    }
-    {
-        const int64_t nb = c.n_examples / L;
-        // partitioned: the peers' row lists take 2 G (LA + LW) ints per slot -> a shorter window
-        int64_t win = c.index_window > 0 ? c.index_window : (a.part ? 256 : 2048);
-        if (win > nb) win = nb;
-        a.index_window = win < 1 ? 1 : win;
-    }
-    int bbits = 1;
-    while ((1 << bbits) < L) ++bbits;
-    a.posbits = 31 - bbits;
-    if (c.max_row_nnz >= (1 << a.posbits)) {
-        delete p;
-        return fail(RAE_E_INVALID, "an example has too many features for the record encoding");
-    }
-    // parameter / dense-row partial slots for the regulariser
-    a.nregC = n_ctiles(c.decoder, c.embed, c.relations) + n_rtiles(c.decoder, c.embed, c.relations);
-    p->grid_dense = 1024;
-    a.nregW = a.reg_on ? p->grid_dense : 0;
-
-    // workspace
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off += (bytes + 255) & ~size_t(255);
-        return o;
+    auto bail = [p](const char* what, hipError_t e) {
+        rae_plan_destroy(p);
+        return fail(RAE_E_HIP, e == hipSuccess ? std::string(what)
+                                               : std::string(what) + ": " + hipGetErrorString(e));
     };
-    const size_t o_cursor = take(8), o_zero = take(8), o_err = take(8), o_base = take(8);
-    const size_t W_ = (size_t)a.index_window;
-    const size_t o_srecA = take(4ull * W_ * a.RA), o_urowA = take(16ull * W_ * a.RA);
-    const size_t o_srecW = take(4ull * W_ * a.RW), o_urowW = take(16ull * W_ * a.RW);
-    const size_t o_skeyA = take(8ull * W_ * a.RA), o_skeyW = take(8ull * W_ * a.RW);
-    const size_t o_gidx = take(4ull * W_ * 4 * RAE_IDX_HMAX);
-    const size_t o_pcls = take(16ull * W_ * 2 * RAE_IDX_HMAX);
-    a.VCA = a.RA / (RAE_VHEAVY + 1) + 1;       // very heavy rows per batch are fewer than this
-    a.VCW = a.RW / (RAE_VHEAVY + 1) + 1;
-    // the update's dispatch table: every unique row is at most one task (TC = records), and
-    // NVC very heavy rows get a workgroup each (L / RAE_NVC_DIV, at least 32 -- the rest run as
-    // wave tasks)
-    a.TC = a.RA + a.RW;
-    {
-        const int Lo = a.part ? (L + a.G - 1) / a.G : L;     // the rows this rank updates
-        const int nvc = Lo / RAE_NVC_DIV > RAE_NVC_MIN ? Lo / RAE_NVC_DIV : RAE_NVC_MIN;
-        a.NVC = nvc < a.VCA + a.VCW ? nvc : a.VCA + a.VCW;
-        // large global batches: very heavy rows with at least 2 RAE_HCH records split into
-        // floor(records / RAE_HCH) chunks (every chunk a workgroup task: NVC >= HF + 1 >
-        // records / RAE_HCH, the most chunks a batch can have -- rae_index.hpp build_batch_tasks)
-        a.hch = (c.heavy_chunk == RAE_HCHUNK_ON ||
-                 (c.heavy_chunk == RAE_HCHUNK_AUTO && L >= RAE_HCH_MINL)) ? RAE_HCH : 0;
-        if (a.hch) {
-            a.HF = (a.RA + a.RW) / a.hch + 1;
-            if (a.NVC < a.HF + 1) a.NVC = a.HF + 1;
-            a.hps = ((c.embed + 3) & ~3) + 4 > ((c.relations + 3) & ~3) ? ((c.embed + 3) & ~3) + 4
-                                                                       : ((c.relations + 3) & ~3);
-        }
-    }
-    const size_t o_thdr = take(16 * W_), o_task = take(16ull * W_ * a.TC);
-    const size_t o_vtask = take(16ull * W_ * a.NVC);
-    const size_t o_hfin = a.hch ? take(16ull * W_ * a.HF) : 0;
-    const size_t o_hpart = a.hch ? take(4ull * a.NVC * a.hps) : 0;
-    {
-        const int NJd = 2 + 2 * c.neg_samples;
-        int cap = c.max_row_nnz > 0 ? c.max_row_nnz : 1;
-        if (cap > 256) cap = 256;                    // the fast path's feature capacity
-        a.dcap = cap;
-        a.dstride = ((2 + NJd + cap) + 31) & ~31;     // whole 128-B lines per example
-    }
-    // private rows (rows one record of the global batch references, updated per example by the
-    // update launch): plans without a regulariser whose record slots fit one wave (NJ <= 64);
-    // the example's features from its descriptor (<= dcap, <= 32).  Several ranks: every rank's
-    // update takes the private rows it updates (replicated: all; partitioned: its own), so the
-    // descriptors cover the whole global batch
-    // auto: single-rank and replicated plans below a global batch of RAE_PRIV_MAXL; at larger
-    // batches and in the partitioned update (a rank's own private rows: a few per example) the
-    // row tasks do them faster (profiles/r04_ab.txt)
-    const bool priv_ok = !a.reg_on && NJ <= 64;
-    a.priv = (priv_ok && (c.priv_rows == RAE_PRIV_ON ||
-                          (c.priv_rows == RAE_PRIV_AUTO && !a.part && L < RAE_PRIV_MAXL))) ? 1 : 0;
-    a.dnx = (a.priv && c.world_size > 1) ? L : c.batch_size;
-    a.d0 = a.dnx == L ? c.rank * c.batch_size : 0;
-    const size_t o_desc = take(4ull * W_ * a.dnx * a.dstride);
-    const size_t o_reg = take(16ull * (a.nregC + a.nregW + 1));
-    const size_t o_gws = a.reg_on ? take(4ull * c.n_features * c.relations) : 0;
-    // partitioned data-parallel update: list capacities are the worst cases of one rank's
-    // l examples (every entity id distinct; the largest global batch's features)
-    a.LA = a.part ? c.batch_size * NJ : 0;
-    a.LW = a.part ? a.RW : 0;
-    const size_t o_dpl = a.part ? take(4ull * W_ * dpl_slot_ints(a.G, a.LA, a.LW)) : 0;
-    const size_t o_dpc = a.part ? take(4ull * W_ * 2 * a.G * 2) : 0;
-    const size_t o_dpm = take(16);
-    // peer-to-peer exchange: the peers' mapped buffers and this rank's expected signal counts
-    const size_t o_peers = take(sizeof(PeerBufs) * (size_t)c.world_size);
-    const size_t o_pexp = take(4ull * 2 * c.world_size);
-    // pipelined peer-to-peer form: two parities of row-mark bytes over the owned rows
-    a.pipe = (c.dp_xchg == RAE_XCHG_P2P_PIPE && c.world_size > 1) ? 1 : 0;
-    a.pmA = a.pipe ? (int)((((c.n_entities + c.world_size - 1) / c.world_size + 3) / 4 + 3) & ~3) : 0;
-    a.pmW = a.pipe ? (int)((((c.n_features + c.world_size - 1) / c.world_size + 3) / 4 + 3) & ~3) : 0;
-    const size_t o_pm = a.pipe ? take(4ull * 2 * (a.pmA + a.pmW)) : 0;
-    const bool bil = c.decoder != RAE_DEC_SP;
-    a.bf16 = (bil && c.mfma_bf16) ? 1 : 0;
-    // bf16 dP with LDS-staged R slices (k_bil_dp2): the C5 shape compiled exactly, other
-    // shapes up to r = 256, K = 128 padded; float4 rows needed (r, K multiples of 4)
-    // dP contraction form: in the second M-tile pass (bf16, m <= 128) by default; k_bil_dp2
-    // (bf16, LDS-staged R slices: the C5 shape compiled exactly, others up to r = 256, m = 128
-    // padded; float4 rows) or the strided k_bil_dp otherwise / on request
-    const bool mt_ok = bil && c.mfma_bf16 && c.relations <= 128;
-    const bool dp2_ok = a.bf16 && c.embed % 4 == 0 && c.relations % 4 == 0 &&
-                        (((c.embed + 31) / 32 == 7 && (c.relations + 15) / 16 == 7) ||
-                         (c.embed <= 256 && c.relations <= 128));
-    const bool mtdp = mt_ok && (c.bil_dp == RAE_BILDP_AUTO || c.bil_dp == RAE_BILDP_MTILE);
-    p->dp2 = 0;
-    if (!mtdp && dp2_ok && c.bil_dp != RAE_BILDP_STRIDED)
-        p->dp2 = ((c.embed + 31) / 32 == 7 && (c.relations + 15) / 16 == 7) ? 1 : 2;
-    a.nib = bil ? (p->dp2 ? (c.embed + RAE_IB2 - 1) / RAE_IB2 : (c.embed + RAE_IB - 1) / RAE_IB) : 0;
-    const size_t o_dpp = bil ? take(4ull * a.nib * c.batch_size * c.relations) : 0;
-    a.r4 = align4(c.embed);
-    const int64_t nbi_mt = (c.embed + RAE_MTI - 1) / RAE_MTI, nbj_mt = (c.embed + RAE_MTJ - 1) / RAE_MTJ;
-    const size_t o_mtv = bil ? take(4ull * nbj_mt * c.batch_size * a.r4) : 0;
-    const size_t o_mtw = bil ? take(4ull * nbi_mt * c.batch_size * a.r4) : 0;
-    a.nmtp = (int)(nbi_mt * nbj_mt);
-    const size_t o_mtp = mtdp ? take(4ull * a.nmtp * c.batch_size * c.relations) : 0;
-    // split SP forward (rae_sp_split.hpp) for runtime shapes whose decoder matrices stream
-    // through every example's workgroup (r*m > RAE_SPLIT_RM; C4: 90 k), or on request
-    p->sp_split = !bil && (c.sp_forward == RAE_SPFWD_SPLIT ||
-                           (c.sp_forward == RAE_SPFWD_AUTO &&
-                            (int64_t)c.embed * c.relations > RAE_SPLIT_RM));
-    const size_t o_sps = p->sp_split ? take(4ull * sps_stride(c.embed) * c.batch_size) : 0;
-    a.privnf = a.priv ? (a.dcap < 32 ? a.dcap : 32) : 0;
-    a.privc = (a.priv && a.part && c.world_size > 1) ? 1 : 0;
-    const size_t o_pmask = a.priv ? take(16ull * W_ * L) : 0;
-    a.Lp = (L + 31) / 32 * 32;
-    a.fuse_prep = (a.bf16 && c.world_size == 1 && c.bil_prep == RAE_BILPREP_AUTO) ? 1 : 0;
-    const size_t o_fac = a.bf16 ? take(16ull * c.embed * a.Lp) : 0;
-    const size_t o_vb = a.lay.wire ? take(4ull * a.vbs * L) : 0;
-    const size_t o_dwb = a.dpart ? take(4ull * a.dws * L) : 0;
-    const size_t o_pfr = a.bf16 ? take(16ull * (a.Lp / 32) * ((c.relations + 15) / 16) * 64) : 0;
-    hipError_t e = hipMalloc(&p->ws, off);
-    if (e != hipSuccess) {
-        delete p;
-        return fail(RAE_E_HIP, std::string("hipMalloc workspace: ") + hipGetErrorString(e));
-    }
-    (void)hipMemset(p->ws, 0, off);
+    const size_t bytes = p->arena.bytes;
+    hipError_t e = hipMalloc(&p->ws, bytes);
+    if (e != hipSuccess) return bail("hipMalloc workspace", e);
+    (void)hipMemset(p->ws, 0, bytes);
     e = hipHostMalloc(reinterpret_cast<void**>(&p->h_err), sizeof(int), hipHostMallocDefault);
-    if (e != hipSuccess) {
-        (void)hipFree(p->ws);
-        delete p;
-        return fail(RAE_E_HIP, std::string("hipHostMalloc: ") + hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return bail("hipHostMalloc", e);
     *p->h_err = 0;
-    if (c.dp_xchg != RAE_XCHG_COLLECTIVE) {
+    if (cfg->dp_xchg != RAE_XCHG_COLLECTIVE) {
         // the peers add to these words over xGMI and this rank polls them: uncached (no L2
         // line of them can go stale; rae_p2p.hpp "Visibility across GPUs")
-        e = hipExtMallocWithFlags(reinterpret_cast<void**>(&p->d_sig), 4ull * 2 * c.world_size,
-                                  hipDeviceMallocUncached);
-        if (e == hipSuccess) e = hipMemset(p->d_sig, 0, 4ull * 2 * c.world_size);
-        if (e != hipSuccess) {
-            (void)hipFree(p->ws);
-            (void)hipHostFree(p->h_err);
-            delete p;
-            return fail(RAE_E_HIP, std::string("hipMalloc signals: ") + hipGetErrorString(e));
-        }
+        const size_t sb = 4ull * 2 * cfg->world_size;
+        e = hipExtMallocWithFlags(reinterpret_cast<void**>(&p->d_sig), sb, hipDeviceMallocUncached);
+        if (e == hipSuccess) e = hipMemset(p->d_sig, 0, sb);
+        if (e != hipSuccess) return bail("hipMalloc signals", e);
     }
-    p->d_cursor = reinterpret_cast<int64_t*>(p->ws + o_cursor);
-    p->d_zero = reinterpret_cast<int64_t*>(p->ws + o_zero);
-    p->d_err = reinterpret_cast<int*>(p->ws + o_err);
-    a.base_cost = reinterpret_cast<float*>(p->ws + o_base);
-    a.srecA = reinterpret_cast<int32_t*>(p->ws + o_srecA);
-    a.urowA = reinterpret_cast<int32_t*>(p->ws + o_urowA);
-    a.srecW = reinterpret_cast<int32_t*>(p->ws + o_srecW);
-    a.urowW = reinterpret_cast<int32_t*>(p->ws + o_urowW);
-    a.skeyA = reinterpret_cast<unsigned long long*>(p->ws + o_skeyA);
-    a.skeyW = reinterpret_cast<unsigned long long*>(p->ws + o_skeyW);
-    a.gidx = reinterpret_cast<int32_t*>(p->ws + o_gidx);
-    a.pcls = reinterpret_cast<int32_t*>(p->ws + o_pcls);
-    a.thdr = reinterpret_cast<int32_t*>(p->ws + o_thdr);
-    a.task = reinterpret_cast<int32_t*>(p->ws + o_task);
-    a.vtask = reinterpret_cast<int32_t*>(p->ws + o_vtask);
-    a.hfin = a.hch ? reinterpret_cast<int32_t*>(p->ws + o_hfin) : nullptr;
-    a.hpart = a.hch ? reinterpret_cast<float*>(p->ws + o_hpart) : nullptr;
-
-    a.desc = reinterpret_cast<int32_t*>(p->ws + o_desc);
-    a.regpart = reinterpret_cast<double*>(p->ws + o_reg);
-    a.gWs = a.reg_on ? reinterpret_cast<float*>(p->ws + o_gws) : nullptr;
-    a.dPpart = bil ? reinterpret_cast<float*>(p->ws + o_dpp) : nullptr;
-    a.sps = p->sp_split ? reinterpret_cast<float*>(p->ws + o_sps) : nullptr;
-    a.spss = sps_stride(c.embed);
-    a.mtV = bil ? reinterpret_cast<float*>(p->ws + o_mtv) : nullptr;
-    a.mtW = bil ? reinterpret_cast<float*>(p->ws + o_mtw) : nullptr;
-    a.mtP = mtdp ? reinterpret_cast<float*>(p->ws + o_mtp) : nullptr;
-    a.facT = a.bf16 ? reinterpret_cast<float*>(p->ws + o_fac) : nullptr;
-    a.pfrag = a.bf16 ? reinterpret_cast<uint4*>(p->ws + o_pfr) : nullptr;
-    a.err = p->d_err;
-    a.cursor = p->d_cursor;
-    a.dpl = a.part ? reinterpret_cast<int32_t*>(p->ws + o_dpl) : nullptr;
-    a.dpc = a.part ? reinterpret_cast<int32_t*>(p->ws + o_dpc) : nullptr;
-    a.dpmax = reinterpret_cast<int*>(p->ws + o_dpm);
-    a.xchg = c.dp_xchg;
-    a.peers = reinterpret_cast<PeerBufs*>(p->ws + o_peers);
-    a.p2p_expect = reinterpret_cast<unsigned*>(p->ws + o_pexp);
-    a.pm = a.pipe ? reinterpret_cast<uint32_t*>(p->ws + o_pm) : nullptr;
-    a.pmask = a.priv ? reinterpret_cast<int32_t*>(p->ws + o_pmask) : nullptr;
-    if (a.lay.wire) a.vb = reinterpret_cast<float*>(p->ws + o_vb);
-    if (a.dpart) a.dwb = reinterpret_cast<float*>(p->ws + o_dwb);
-
-    const int ex_floats = example_smem_floats(c.decoder, c.relations, c.embed, c.neg_samples);
-    const size_t smem_ex = 4ull * ex_floats;
-    // k_idx_sort<big>: keys, scan scratch, segment starts (the fast form: RAE_IDX_FAST keys)
-    p->smem_idx = 8ull * RAE_KCAP + 4ull * 64 + 4ull * RAE_KCAP;
-    p->smem_idxf = 8ull * RAE_IDX_FAST + 4ull * 64 + 4ull * RAE_IDX_FAST;
-    p->smem_fwd = smem_ex;
-    p->smem_spe = p->sp_split ? 4ull * example_smem_floats(0, c.relations, c.embed, 0) : 0;
-    p->smem_spd = p->sp_split ? 4ull * sp_dec_side_smem_floats(c.embed, c.neg_samples) : 0;
-    p->smem_dec = bil ? 4ull * bil_dec_smem_floats(c.embed, c.neg_samples) : 0;
-    // the M-tile passes: bf16 blocks need m <= 128 (four K steps of 32 per fragment set)
-    p->mt_bf16 = bil && a.bf16 && c.relations <= 128;
-    p->smem_mt = bil ? bil_mt_lds_bytes(c.relations, p->mt_bf16) : 0;
-    // the first pass never stages the transposed image (dP rides on the second): with half the
-    // LDS, two of its workgroups fit a CU and all (r/8)(r/16) start at once
-    p->smem_mt0 = (bil && p->mt_bf16) ? (size_t)RAE_MTI * RAE_MTJ * (((c.relations + 31) / 32 * 32) + 8) * 2
-                                      : p->smem_mt;
-
-    if (p->smem_mt > RAE_MT_LDS_MAX) {        // fp32 block too large to stage (m > 320)
-        p->mt_direct = true;
-        p->smem_mt = 0;
-    }
-    if (p->smem_fwd > 160 * 1024 || p->smem_idx > 160 * 1024 || p->smem_dec > 160 * 1024) {
-        (void)hipFree(p->ws);
-        delete p;
-        return fail(RAE_E_INVALID, "configuration needs more than 160 KiB LDS per example "
-                                   "workgroup (relations / embed / neg_samples too large)");
-    }
-    p->grid_fwd = c.batch_size;
-    const int64_t gu = update_grid(c.decoder, c.embed, c.relations, a.TC, a.NVC, L, a.priv,
-                                   a.privc, a.part ? a.G : 1);
-    if (gu >= (1ll << 31)) {
-        (void)hipFree(p->ws);
-        delete p;
-        return fail(RAE_E_INVALID, "update grid too large");
-    }
-    p->grid_update = (int)gu;
-    {
-        const void* fns[] = {(const void*)k_forward<true, DimsC3>,
-                             (const void*)k_forward<false, DimsC2>,
-                             (const void*)k_forward<true, DynDims>,
-                             (const void*)k_forward<false, DynDims>,
-                             (const void*)k_bil_enc<true>, (const void*)k_bil_enc<false>,
-                             (const void*)k_bil_enc_fast<DimsC3>,
-                             (const void*)k_sp_dec<true>, (const void*)k_sp_dec<false>};
-        for (const void* f : fns)
-            (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)p->smem_fwd);
-        if (p->sp_split) {
-            (void)hipFuncSetAttribute((const void*)k_sp_enc<true>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->smem_spe);
-            (void)hipFuncSetAttribute((const void*)k_sp_enc<false>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->smem_spe);
-        }
-        if (bil) {
-            (void)hipFuncSetAttribute((const void*)k_bil_dp2<7, 7>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)dp2_lds_bytes<7, 7>());
-            (void)hipFuncSetAttribute((const void*)k_bil_dp2<8, 8>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)dp2_lds_bytes<8, 8>());
-            (void)hipFuncSetAttribute((const void*)k_bil_mt<true>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->smem_mt);
-            (void)hipFuncSetAttribute((const void*)k_bil_mt<true, false, false>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->smem_mt);
-            (void)hipFuncSetAttribute((const void*)k_bil_mt<false>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->smem_mt);
-            (void)hipFuncSetAttribute((const void*)k_bil_dec<true>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->smem_dec);
-            (void)hipFuncSetAttribute((const void*)k_bil_dec<false>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->smem_dec);
-        }
-        (void)hipFuncSetAttribute((const void*)k_idx_sort<true>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->smem_idx);
-        (void)hipFuncSetAttribute((const void*)k_build_dplists,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)(4 * RAE_DPL_KEYS + 4 * 32));
-    }
+    p->bind(p->ws);
+    plan_set_kernel_attributes(p);
+    StepArgs& a = p->args;
     a.sig = p->d_sig;
-    a.p2p_timeout = RAE_P2P_TIMEOUT_DEFAULT;
     if (a.sig) {                 // this rank's own entry of the peer table
         const PeerBufs own{a.ex, a.W, a.A, a.Ab, a.sig};
-        if (hipMemcpy(a.peers + c.rank, &own, sizeof(own), hipMemcpyHostToDevice) != hipSuccess) {
-            rae_plan_destroy(p);
-            return fail(RAE_E_HIP, "peer table");
-        }
+        if (hipMemcpy(a.peers + cfg->rank, &own, sizeof(own), hipMemcpyHostToDevice) != hipSuccess)
+            return bail("peer table", hipSuccess);
     }
     *out = p;
     return RAE_OK;
@@ -1217,15 +775,12 @@ static void launch_fwd_sp(rae_plan* p, const StepArgs& a, hipStream_t st) {
     const dim3 gr(p->grid_fwd), bt(RAE_FBT);
     if (p->sp_split) {
         const dim3 gcp(sp_cp_tasks(a.l, a.r)), gct(sp_ctdw_tasks(a.l, a.m));   // WG per tile
-        if (p->v4) RAE_LAUNCH(p, k_sp_enc<true>, gr, bt, p->smem_spe, st, a);
-        else RAE_LAUNCH(p, k_sp_enc<false>, gr, bt, p->smem_spe, st, a);
-        if (a.m % 4 == 0) RAE_LAUNCH(p, k_sp_cp<true>, gcp, dim3(RAE_BT), 0, st, a);
-        else RAE_LAUNCH(p, k_sp_cp<false>, gcp, dim3(RAE_BT), 0, st, a);
         const dim3 gsd(RAE_SPD_NP * p->grid_fwd);          // a workgroup per (example, piece)
-        if (p->v4) RAE_LAUNCH(p, k_sp_dec<true>, gsd, bt, p->smem_spd, st, a);
-        else RAE_LAUNCH(p, k_sp_dec<false>, gsd, bt, p->smem_spd, st, a);
-        if (a.r % 4 == 0) RAE_LAUNCH(p, k_sp_ctdw<true>, gct, dim3(RAE_DW_BT), 0, st, a);
-        else RAE_LAUNCH(p, k_sp_ctdw<false>, gct, dim3(RAE_DW_BT), 0, st, a);
+        with_bool(p->v4, [&](auto V) { RAE_LAUNCH(p, k_sp_enc<RAE_CV(V)>, gr, bt, p->smem_spe, st, a); });
+        with_bool(a.m % 4 == 0, [&](auto V) { RAE_LAUNCH(p, k_sp_cp<RAE_CV(V)>, gcp, dim3(RAE_BT), 0, st, a); });
+        with_bool(p->v4, [&](auto V) { RAE_LAUNCH(p, k_sp_dec<RAE_CV(V)>, gsd, bt, p->smem_spd, st, a); });
+        with_bool(a.r % 4 == 0,
+                  [&](auto V) { RAE_LAUNCH(p, k_sp_ctdw<RAE_CV(V)>, gct, dim3(RAE_DW_BT), 0, st, a); });
         return;
     }
     const bool c3 = a.m == 100 && a.r == 200 && a.s == 20;
@@ -1268,10 +823,8 @@ static void launch_fwd_dp(rae_plan* p, const StepArgs& a, hipStream_t st) {
         RAE_LAUNCH(p, (k_bil_dp2<7, 7>), dim3(a.nib), dim3(dp2_threads<7, 7>()), lds77, st, a);
     else if (p->dp2 == 2)
         RAE_LAUNCH(p, (k_bil_dp2<8, 8>), dim3(a.nib), dim3(dp2_threads<8, 8>()), lds88, st, a);
-    else if (a.bf16)
-        RAE_LAUNCH(p, k_bil_dp<true>, dim3(gd), dim3(RAE_BT), 0, st, a);
     else
-        RAE_LAUNCH(p, k_bil_dp<false>, dim3(gd), dim3(RAE_BT), 0, st, a);
+        with_bool(a.bf16, [&](auto B) { RAE_LAUNCH(p, k_bil_dp<RAE_CV(B)>, dim3(gd), dim3(RAE_BT), 0, st, a); });
 }
 
 // peer-to-peer exchange grids (every rank the same: the peers expect these many signals)
@@ -1312,8 +865,7 @@ static int launch_forward(rae_plan* p, const int64_t* cursor, int64_t off, hipSt
         if (a.dpart)          // this rank's dense partials into its records, before the exchange
             RAE_LAUNCH(p, k_dpart, dim3(dpart_tasks(a.r, a.m)), dim3(RAE_BT), 0, st, a);
     }
-    else if (p->v4) launch_fwd_bil<true>(p, a, st);
-    else launch_fwd_bil<false>(p, a, st);
+    else with_bool(p->v4, [&](auto V) { launch_fwd_bil<RAE_CV(V)>(p, a, st); });
     if (p2p)                  // this rank's records into every peer's exchange buffer
     {
         // (pipelined: + blocks clearing the next batch's row marks)
@@ -1347,67 +899,33 @@ static void launch_update_b(rae_plan* p, dim3 gu, dim3 bt, hipStream_t st, const
         constexpr size_t lu = 4 * update_lds_floats<V4, 2>();
         if (RAE_BIL_FUSED_UPD && lr >= lu) {
             const dim3 gf(gu.x + gr.x);
-            if (a.pipe) {     // (the pipelined peer-to-peer form's row pushes compiled in)
-                if (p->q == 1) RAE_LAUNCH(p, (k_bil_update<OPT, V4, 1, true>), gf, bt, lr, st, a, (int)gu.x);
-                else RAE_LAUNCH(p, (k_bil_update<OPT, V4, 2, true>), gf, bt, lr, st, a, (int)gu.x);
-            } else {
-                if (p->q == 1) RAE_LAUNCH(p, (k_bil_update<OPT, V4, 1>), gf, bt, lr, st, a, (int)gu.x);
-                else RAE_LAUNCH(p, (k_bil_update<OPT, V4, 2>), gf, bt, lr, st, a, (int)gu.x);
-            }
+            // (PP: the pipelined peer-to-peer form's row pushes compiled in)
+            with_bool(a.pipe, [&](auto PP) { with_q(p->q, [&](auto Q) {
+                RAE_LAUNCH(p, (k_bil_update<OPT, V4, RAE_CV(Q), RAE_CV(PP)>), gf, bt, lr, st, a, (int)gu.x);
+            }); });
             return;
         }
-        if (lr) RAE_LAUNCH(p, (k_bil_rows<OPT, true>), gr, bt, lr, st, a);
-        else RAE_LAUNCH(p, (k_bil_rows<OPT, false>), gr, bt, 0, st, a);
-        if (a.pipe) {
-            if (p->q == 1) RAE_LAUNCH(p, (k_update_bil<OPT, V4, 1, true>), gu, bt, 0, st, a);
-            else RAE_LAUNCH(p, (k_update_bil<OPT, V4, 2, true>), gu, bt, 0, st, a);
-        } else {
-            if (p->q == 1) RAE_LAUNCH(p, (k_update_bil<OPT, V4, 1>), gu, bt, 0, st, a);
-            else RAE_LAUNCH(p, (k_update_bil<OPT, V4, 2>), gu, bt, 0, st, a);
-        }
+        with_bool(lr != 0, [&](auto LDS) {
+            RAE_LAUNCH(p, (k_bil_rows<OPT, RAE_CV(LDS)>), gr, bt, lr, st, a);
+        });
+        with_bool(a.pipe, [&](auto PP) { with_q(p->q, [&](auto Q) {
+            RAE_LAUNCH(p, (k_update_bil<OPT, V4, RAE_CV(Q), RAE_CV(PP)>), gu, bt, 0, st, a);
+        }); });
     } else {
         // the data-parallel SP update (wire records: vectors in the vector buffer, dense
         // partials) and the single-rank one are separate instantiations
-        if (a.lay.wire) {
-            if (p->q == 1) RAE_LAUNCH(p, (k_update<OPT, V4, 1, true>), gu, bt, 0, st, a);
-            else RAE_LAUNCH(p, (k_update<OPT, V4, 2, true>), gu, bt, 0, st, a);
-        } else {
-            if (p->q == 1) RAE_LAUNCH(p, (k_update<OPT, V4, 1, false>), gu, bt, 0, st, a);
-            else RAE_LAUNCH(p, (k_update<OPT, V4, 2, false>), gu, bt, 0, st, a);
-        }
+        with_bool(a.lay.wire != 0, [&](auto WIRE) { with_q(p->q, [&](auto Q) {
+            RAE_LAUNCH(p, (k_update<OPT, V4, RAE_CV(Q), RAE_CV(WIRE)>), gu, bt, 0, st, a);
+        }); });
     }
-}
-template <int OPT, bool V4>
-static void launch_update_v(rae_plan* p, dim3 gu, dim3 bt, hipStream_t st, const StepArgs& a) {
-    if (a.dec == RAE_DEC_SP) launch_update_b<OPT, V4, false>(p, gu, bt, st, a);
-    else launch_update_b<OPT, V4, true>(p, gu, bt, st, a);
-}
-template <int OPT>
-static void launch_update_q(rae_plan* p, dim3 gu, dim3 bt, hipStream_t st, const StepArgs& a) {
-    if (p->v4) launch_update_v<OPT, true>(p, gu, bt, st, a);
-    else launch_update_v<OPT, false>(p, gu, bt, st, a);
 }
 
 // k_heavy_fin for the plan's optimizer / vector width / row slots (PP: pipelined pushes)
 template <bool PP>
 static void launch_heavy_fin(rae_plan* p, dim3 gh, dim3 bt, hipStream_t st, const StepArgs& a) {
-    if (a.opt == RAE_OPT_ADAGRAD) {
-        if (p->v4) {
-            if (p->q == 1) RAE_LAUNCH(p, (k_heavy_fin<0, true, 1, PP>), gh, bt, 0, st, a);
-            else RAE_LAUNCH(p, (k_heavy_fin<0, true, 2, PP>), gh, bt, 0, st, a);
-        } else {
-            if (p->q == 1) RAE_LAUNCH(p, (k_heavy_fin<0, false, 1, PP>), gh, bt, 0, st, a);
-            else RAE_LAUNCH(p, (k_heavy_fin<0, false, 2, PP>), gh, bt, 0, st, a);
-        }
-    } else {
-        if (p->v4) {
-            if (p->q == 1) RAE_LAUNCH(p, (k_heavy_fin<1, true, 1, PP>), gh, bt, 0, st, a);
-            else RAE_LAUNCH(p, (k_heavy_fin<1, true, 2, PP>), gh, bt, 0, st, a);
-        } else {
-            if (p->q == 1) RAE_LAUNCH(p, (k_heavy_fin<1, false, 1, PP>), gh, bt, 0, st, a);
-            else RAE_LAUNCH(p, (k_heavy_fin<1, false, 2, PP>), gh, bt, 0, st, a);
-        }
-    }
+    with_opt(a.opt, [&](auto O) { with_bool(p->v4, [&](auto V) { with_q(p->q, [&](auto Q) {
+        RAE_LAUNCH(p, (k_heavy_fin<RAE_CV(O), RAE_CV(V), RAE_CV(Q), PP>), gh, bt, 0, st, a);
+    }); }); });
 }
 
 static int launch_update(rae_plan* p, const int64_t* cursor, int64_t off, hipStream_t st) {
@@ -1421,23 +939,21 @@ static int launch_update(rae_plan* p, const int64_t* cursor, int64_t off, hipStr
     if (a.lay.wire)           // the vectors the wire records left out, for the whole batch
     {
         const dim3 gv(ceil_div(vrec_tasks(a.L, a.r), RAE_NWAVE));
-        if (a.m % 4 == 0) RAE_LAUNCH(p, k_vrec<true>, gv, bt, 0, st, a);
-        else RAE_LAUNCH(p, k_vrec<false>, gv, bt, 0, st, a);
+        with_bool(a.m % 4 == 0, [&](auto V) { RAE_LAUNCH(p, k_vrec<RAE_CV(V)>, gv, bt, 0, st, a); });
     }
-    if (a.opt == RAE_OPT_ADAGRAD) launch_update_q<0>(p, gu, bt, st, a);
-    else launch_update_q<1>(p, gu, bt, st, a);
+    with_opt(a.opt, [&](auto O) { with_bool(p->v4, [&](auto V) {
+        with_bool(a.dec == RAE_DEC_SP, [&](auto SP) {
+            launch_update_b<RAE_CV(O), RAE_CV(V), !RAE_CV(SP)>(p, gu, bt, st, a);
+        });
+    }); });
     HIPCHK(hipGetLastError());
     if (a.hch) {              // the rows split into chunks: their chunk sums combined + updated
         const dim3 gh(ceil_div(a.HF, RAE_NWAVE));
-        if (a.pipe) launch_heavy_fin<true>(p, gh, bt, st, a);
-        else launch_heavy_fin<false>(p, gh, bt, st, a);
+        with_bool(a.pipe, [&](auto PP) { launch_heavy_fin<RAE_CV(PP)>(p, gh, bt, st, a); });
         HIPCHK(hipGetLastError());
     }
     if (a.reg_on) {
-        if (a.opt == RAE_OPT_ADAGRAD)
-            RAE_LAUNCH(p, (k_dense_w<0>), dim3(p->grid_dense), bt, 0, st, a);
-        else
-            RAE_LAUNCH(p, (k_dense_w<1>), dim3(p->grid_dense), bt, 0, st, a);
+        with_opt(a.opt, [&](auto O) { RAE_LAUNCH(p, k_dense_w<RAE_CV(O)>, dim3(p->grid_dense), bt, 0, st, a); });
         HIPCHK(hipGetLastError());
         RAE_LAUNCH(p, k_finalize_cost, dim3(1), dim3(64), 0, st, a);
         HIPCHK(hipGetLastError());
@@ -1565,8 +1081,7 @@ static int launch_dp_move(rae_plan* p, bool pack, const int64_t* cursor, int64_t
     const int64_t waves = (int64_t)a.G * (a.capA + a.capW);
     if (waves == 0) return RAE_OK;
     const dim3 gr((unsigned)((waves + RAE_NWAVE - 1) / RAE_NWAVE));
-    if (pack) RAE_LAUNCH(p, k_dp_move<true>, gr, dim3(RAE_BT), 0, st, a);
-    else RAE_LAUNCH(p, k_dp_move<false>, gr, dim3(RAE_BT), 0, st, a);
+    with_bool(pack, [&](auto PACK) { RAE_LAUNCH(p, k_dp_move<RAE_CV(PACK)>, gr, dim3(RAE_BT), 0, st, a); });
     p->t_start = p->t_stop = nullptr;
     HIPCHK(hipGetLastError());
     return RAE_OK;
@@ -1925,17 +1440,15 @@ extern "C" int rae_eval_cost(const rae_eval_args* a, rae_stream_t stream) {
         if (bil) {
             const dim3 ge((unsigned)std::min(ceil_div(n, RAE_EV_NW), 65536));
             const dim3 gm((unsigned)(eval_nbi(r) * eval_nbj(r)));
-            if (v4) {
-                hipLaunchKernelGGL(k_eval_enc<true>, ge, dim3(RAE_EV_BT), 0, st, e);
-                hipLaunchKernelGGL(k_eval_mt<true>, gm, dim3(RAE_EV_MTT), lds_mt, st, e);
-            } else {
-                hipLaunchKernelGGL(k_eval_enc<false>, ge, dim3(RAE_EV_BT), 0, st, e);
-                hipLaunchKernelGGL(k_eval_mt<false>, gm, dim3(RAE_EV_MTT), lds_mt, st, e);
-            }
+            with_bool(v4, [&](auto V) {
+                hipLaunchKernelGGL(k_eval_enc<RAE_CV(V)>, ge, dim3(RAE_EV_BT), 0, st, e);
+                hipLaunchKernelGGL(k_eval_mt<RAE_CV(V)>, gm, dim3(RAE_EV_MTT), lds_mt, st, e);
+            });
         }
         const dim3 gd((unsigned)ceil_div(n, RAE_EV_TE));
-        if (v4) hipLaunchKernelGGL(k_eval_dec<true>, gd, dim3(RAE_EV_BT), lds_dec, st, e);
-        else hipLaunchKernelGGL(k_eval_dec<false>, gd, dim3(RAE_EV_BT), lds_dec, st, e);
+        with_bool(v4, [&](auto V) {
+            hipLaunchKernelGGL(k_eval_dec<RAE_CV(V)>, gd, dim3(RAE_EV_BT), lds_dec, st, e);
+        });
         const int nblk = ceil_div(n, RAE_EV_SUMROWS);
         hipLaunchKernelGGL(k_eval_blocksum, dim3((unsigned)nblk), dim3(RAE_EV_BT), 0, st,
                            (const float*)e.terms, n, partial);

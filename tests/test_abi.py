@@ -4,6 +4,8 @@ import ctypes as C
 import os
 import re
 
+import pytest
+
 from conftest import ROOT
 
 
@@ -140,3 +142,46 @@ def test_plan_create_rejects_unknown_kernel_form(built_lib):
     h = C.c_void_p()
     assert built_lib.rae_plan_create(C.byref(cfg), C.byref(bufs), C.byref(h)) == -1
     assert b"kernel form" in built_lib.rae_last_error()
+
+
+def _rejected_specs():
+    import json
+    from conftest import GOLDEN
+    with open(os.path.join(GOLDEN, "plan_specs.json")) as fh:
+        return [e for e in json.load(fh) if e["lines"][0] != "rc 0"]
+
+
+def _plan_create(lib, config):
+    """rae_plan_create with dummy non-null buffers ("null.<buffer>" keys leave one out)."""
+    from rae import _lib
+    cfg, bufs = _lib.RaeConfig(), _lib.RaeBuffers()
+    dummy = (C.c_float * 4)()
+    for name, _ in bufs._fields_:
+        setattr(bufs, name, C.addressof(dummy))
+    for k, v in config.items():
+        if k.startswith("null."):
+            setattr(bufs, k[5:], None)
+        else:
+            setattr(cfg, k, v)
+    h = C.c_void_p()
+    return lib.rae_plan_create(C.byref(cfg), C.byref(bufs), C.byref(h)), h
+
+
+
+@pytest.mark.parametrize("spec", _rejected_specs(), ids=lambda e: e["name"])
+def test_plan_create_rejects_before_allocating(built_lib, spec):
+    """Every rejection of plan_resolve through the real export, without a GPU: validation ends
+    before anything is allocated, so the message is the check's (as the parent's source words
+    it: tests/golden/plan_specs.json), never a failed hipMalloc's."""
+    rc, h = _plan_create(built_lib, spec["config"])
+    assert rc == -1 and not h.value
+    assert spec["lines"][1] == "err " + built_lib.rae_last_error().decode()
+
+
+def test_plan_create_rejects_null_arguments(built_lib):
+    from rae import _lib
+    cfg, bufs, h = _lib.RaeConfig(), _lib.RaeBuffers(), C.c_void_p()
+    for args in ((None, C.byref(bufs), C.byref(h)), (C.byref(cfg), None, C.byref(h)),
+                 (C.byref(cfg), C.byref(bufs), None)):
+        assert built_lib.rae_plan_create(*args) == -1
+        assert built_lib.rae_last_error() == b"null argument"
