@@ -91,6 +91,37 @@ def test_eval_workspace_is_bounded(built_lib):
     assert b"relations" in lib.rae_last_error()
 
 
+def test_eval_shape_limits_one_step_past(built_lib):
+    """The shape limits include/rae.h states (relations <= 512, a multiple of 4 above 128, <= 320
+    for the bilinear decoders; embed <= 1024; at most 160 KiB of LDS per 16-example tile): the
+    last accepted shape gives a positive size, one step past it gives -1 and rae_last_error
+    names the field."""
+    lib = built_lib
+    SP, RESCAL, HYBRID = 0, 1, 2
+    # the hybrid's tile holds P (m rounded up to 4) and four vectors of r rounded up to 4:
+    # 16 (mS + 4 r4) 4 bytes <= 160 KiB; at m = 4 the largest r is 636
+    r_hyb = max(r for r in range(1, 1025) if 16 * (4 + 4 * ((r + 3) & ~3)) * 4 <= 160 * 1024)
+    assert r_hyb == 636
+    accepted = [(SP, 512, 200), (SP, 128, 200), (SP, 127, 200), (SP, 100, 1024), (SP, 512, 1024),
+                (RESCAL, 320, 24), (HYBRID, 320, 24), (HYBRID, 4, r_hyb)]
+    for dec, m, r in accepted:
+        assert _ws(lib, _args(dec, m, r, 3)) > 0, (dec, m, r, lib.rae_last_error())
+    refused = [(SP, 513, 200, "relations"), (SP, 129, 200, "relations"),
+               (SP, 130, 200, "relations"), (SP, 100, 1025, "embed"),
+               (RESCAL, 324, 24, "relations"), (HYBRID, 324, 24, "relations"),
+               (SP, 512, 1028, "embed"), (HYBRID, 4, r_hyb + 1, "embed"), (HYBRID, 4, 640, "embed")]
+    bad = []
+    for dec, m, r, word in refused:
+        a = _args(dec, m, r, 3)
+        size = _ws(lib, a)
+        msg = lib.rae_last_error().decode()
+        a.workspace_bytes = 1 << 40
+        rc = lib.rae_eval_cost(C.byref(a), None)        # refused before any HIP call
+        if size != -1 or rc != -1 or word not in msg:
+            bad.append((dec, m, r, size, rc, msg))
+    assert not bad, bad
+
+
 def test_cli_eval_cost_flag():
     from rae import cli
     base = ["data.npz", "--model-name", "m", "--decoder", "sp"]
