@@ -364,6 +364,49 @@ typedef struct rae_eval_args {
 int64_t rae_eval_workspace_bytes(const rae_eval_args* a);
 int rae_eval_cost(const rae_eval_args* a, rae_stream_t stream);
 
+/* --- cluster evaluation (get_clusters_sets learning/OieInduction.py:321-340;
+ *     evaluation/OieEvaluation.py:23-44,90-127) ------------------------------------ */
+/* Plan-free and stream-ordered like rae_label / rae_eval_cost: every pointer is a device
+ * pointer, the calls allocate nothing, never synchronise (capturable; the table is zeroed by a
+ * kernel) and check their arguments before the first HIP call.  Integer atomics only: the table
+ * is bit-exact whatever the form, grid size or arrival order.                               */
+#define RAE_CCOUNT_AUTO   0   /* private LDS table per workgroup when it fits, else global      */
+#define RAE_CCOUNT_LDS    1   /* workgroup-private LDS counters, flushed once per workgroup     */
+#define RAE_CCOUNT_GLOBAL 2   /* integer atomics straight into table                             */
+#define RAE_CCOUNT_ACCUMULATE 0x100  /* or-ed into form: add to table (else it is zeroed first) */
+/* LDS budget of the LDS form: relations * (n_gold + 1) 32-bit counters <= 16384 (64 KiB of
+ * gfx950's 160 KiB per workgroup, so two workgroups stay resident per CU and one streams while
+ * the other zeroes or flushes its counters; the flagship 100 x 41 table takes 16 KiB).  AUTO
+ * takes the LDS form within the budget; asking for it beyond the budget is RAE_E_INVALID.   */
+#define RAE_CCOUNT_LDS_CELLS 16384
+
+/* table[(c)*(n_gold+1) + g] += |{ i < nrows : labels[i] == c, gold[i] == g }|,  column n_gold
+ * counts the rows with gold[i] outside [0, n_gold) (unlabelled: -1).  Rows whose label is
+ * outside [0, relations) are skipped (never an out-of-range access).  int64 table.
+ * relations in [1, 512] (no multiple-of-4 rule), n_gold in [0, 4095], nrows >= 0 (nrows == 0
+ * still zeroes the table unless accumulating).  labels / gold need their element alignment
+ * only: they are read 16 bytes at a time between a scalar head and tail.                    */
+int rae_cluster_count(const int64_t* labels, const int32_t* gold, int64_t nrows,
+                      int32_t relations, int32_t n_gold, int32_t form, int64_t* table,
+                      rae_stream_t stream);
+
+/* table -> metrics_out[4] = { f1, precision, recall, numberOfElements } (double) with the
+ * semantics of rae/evaluation.py compute_metrics;  gold_sizes[g] = |G_g| and n_assessable =
+ * |A| are over the WHOLE gold standard of the split (rows that were not labelled -- the
+ * dropped tail -- still count there, as in the reference).  sizes_out (relations int64,
+ * may be NULL) = cluster sizes incl. unlabelled members (get_clusters_size).
+ *   precision = sum n_cg^2 / a_c / |A|, a_c = sum_{g < n_gold} n_cg (a_c == 0 adds nothing)
+ *   recall    = sum n_cg^2 / |G_g| / |A|  (|G_g| == 0 adds nothing)
+ *   n_assessable == 0 -> (0, 0, 0); f1 = 0 when precision = recall = 0; numberOfElements =
+ *   the sum of the whole table; terms are double(n)*double(n)/double(a).
+ * One launch, fixed summation order (bitwise reproducible, a function of the table alone):
+ * within a cluster row lane j of a wave adds columns j, j + 64, ... in order and the 64 lane
+ * sums fold by the xor tree 32, 16, ..., 1; the row sums are then added in cluster order.
+ * gold_sizes may be NULL when n_gold == 0.                                                  */
+int rae_b3_metrics(const int64_t* table, const int64_t* gold_sizes, int64_t n_assessable,
+                   int32_t relations, int32_t n_gold, double* metrics_out,
+                   int64_t* sizes_out, rae_stream_t stream);
+
 /* --- measurement helper (bench.py; no reference counterpart) ------------------------- */
 /* STREAM-style device copy of `bytes` (multiple of 16, 16-byte aligned pointers) with float4
  * loads and stores: the measured HBM ceiling bench.py reports next to the 8 TB/s spec.   */

@@ -25,6 +25,7 @@
 
 #include "../../include/rae.h"
 #include "rae_bilinear.hpp"
+#include "rae_cluster.hpp"
 #include "rae_sp_split.hpp"
 #include "rae_common.hpp"
 #include "rae_dp.hpp"
@@ -1456,5 +1457,91 @@ extern "C" int rae_eval_cost(const rae_eval_args* a, rae_stream_t stream) {
                            a->sums_out, c0 == 0 ? 1 : 0);
         HIPCHK(hipGetLastError());
     }
+    return RAE_OK;
+}
+
+// ---- cluster evaluation ---------------------------------------------------------------------
+extern "C" int rae_cluster_count(const int64_t* labels, const int32_t* gold, int64_t nrows,
+                                 int32_t relations, int32_t n_gold, int32_t form, int64_t* table,
+                                 rae_stream_t stream) {
+    if (!labels) return fail(RAE_E_INVALID, "labels is NULL");
+    if (!gold) return fail(RAE_E_INVALID, "gold is NULL");
+    if (!table) return fail(RAE_E_INVALID, "table is NULL");
+    if (relations < 1 || relations > 512)
+        return fail(RAE_E_INVALID, "relations must be in [1, 512]");
+    if (n_gold < 0 || n_gold > 4095) return fail(RAE_E_INVALID, "n_gold must be in [0, 4095]");
+    if (nrows < 0) return fail(RAE_E_INVALID, "nrows must be >= 0");
+    const bool accumulate = (form & RAE_CCOUNT_ACCUMULATE) != 0;
+    const int kind = form & ~RAE_CCOUNT_ACCUMULATE;
+    if (kind != RAE_CCOUNT_AUTO && kind != RAE_CCOUNT_LDS && kind != RAE_CCOUNT_GLOBAL)
+        return fail(RAE_E_INVALID, "form must be RAE_CCOUNT_AUTO, _LDS or _GLOBAL");
+    if (((uintptr_t)labels & 7) || ((uintptr_t)gold & 3) || ((uintptr_t)table & 7))
+        return fail(RAE_E_INVALID, "labels / gold / table must be aligned to their element size");
+    const int64_t cells = (int64_t)relations * (n_gold + 1);
+    // a workgroup's 32-bit counters hold its share of the rows: nrows / 512 workgroups < 2^31
+    const bool fits = cells <= RAE_CC_LDS_CELLS && nrows < (1ll << 40);
+    if (kind == RAE_CCOUNT_LDS && !fits)
+        return fail(RAE_E_INVALID, "form RAE_CCOUNT_LDS: relations * (n_gold + 1) counters exceed "
+                                   "the LDS budget of 16384 (or nrows >= 2^40)");
+    const bool lds = kind == RAE_CCOUNT_LDS || (kind == RAE_CCOUNT_AUTO && fits);
+    hipStream_t st = (hipStream_t)stream;
+    unsigned long long* tb = (unsigned long long*)table;
+    if (!accumulate) {
+        const int64_t zg = std::min<int64_t>((cells + 255) / 256, 1024);
+        hipLaunchKernelGGL(k_cc_zero, dim3((unsigned)zg), dim3(256), 0, st, tb, (long long)cells);
+        HIPCHK(hipGetLastError());
+    }
+    if (nrows == 0) return RAE_OK;
+    // rows before the first index at which both pointers are 16-byte aligned (GV); with none,
+    // the labels alone are aligned and the gold ids are read as dwords
+    int head = -1;
+    for (int h = 0; h < 4; ++h)
+        if ((((uintptr_t)(labels + h)) & 15) == 0 && (((uintptr_t)(gold + h)) & 15) == 0) {
+            head = h;
+            break;
+        }
+    const bool gv = head >= 0;
+    if (!gv) head = ((uintptr_t)labels & 15) ? 1 : 0;
+    if (head > nrows) head = (int)nrows;
+    const int64_t nq = (nrows - head) >> 2;
+    const int64_t per = (int64_t)RAE_CC_BT * RAE_CC_QPT;
+    int64_t grid = (nq + per - 1) / per;
+    const int64_t cap = lds ? RAE_CC_GRID_LDS : RAE_CC_GRID_GLOBAL;
+    grid = std::max<int64_t>(1, std::min(grid, cap));
+    const size_t shmem = lds ? (size_t)cells * sizeof(unsigned) : 0;
+    const void* fn = lds ? (gv ? (const void*)k_ccount<true, true> : (const void*)k_ccount<true, false>)
+                         : (gv ? (const void*)k_ccount<false, true> : (const void*)k_ccount<false, false>);
+    if (shmem > 48 * 1024)       // large dynamic LDS is opted into per kernel (not a stream operation)
+        HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+    with_bool(lds, [&](auto Lf) {
+        with_bool(gv, [&](auto Gf) {
+            hipLaunchKernelGGL((k_ccount<RAE_CV(Lf), RAE_CV(Gf)>), dim3((unsigned)grid),
+                               dim3(RAE_CC_BT), shmem, st, (const long long*)labels,
+                               (const int*)gold, (long long)nrows, head, (int)relations,
+                               (int)n_gold, tb);
+        });
+    });
+    HIPCHK(hipGetLastError());
+    return RAE_OK;
+}
+
+extern "C" int rae_b3_metrics(const int64_t* table, const int64_t* gold_sizes, int64_t n_assessable,
+                              int32_t relations, int32_t n_gold, double* metrics_out,
+                              int64_t* sizes_out, rae_stream_t stream) {
+    if (!table) return fail(RAE_E_INVALID, "table is NULL");
+    if (!metrics_out) return fail(RAE_E_INVALID, "metrics_out is NULL");
+    if (relations < 1 || relations > 512)
+        return fail(RAE_E_INVALID, "relations must be in [1, 512]");
+    if (n_gold < 0 || n_gold > 4095) return fail(RAE_E_INVALID, "n_gold must be in [0, 4095]");
+    if (n_gold > 0 && !gold_sizes) return fail(RAE_E_INVALID, "gold_sizes is NULL");
+    if (n_assessable < 0) return fail(RAE_E_INVALID, "n_assessable must be >= 0");
+    if (((uintptr_t)table & 7) || ((uintptr_t)gold_sizes & 7) || ((uintptr_t)metrics_out & 7) ||
+        ((uintptr_t)sizes_out & 7))
+        return fail(RAE_E_INVALID, "table / gold_sizes / metrics_out / sizes_out must be 8-byte aligned");
+    hipLaunchKernelGGL(k_b3, dim3(1), dim3(RAE_B3_BT), 0, (hipStream_t)stream,
+                       (const long long*)table, (const long long*)gold_sizes,
+                       (long long)n_assessable, (int)relations, (int)n_gold, metrics_out,
+                       (long long*)sizes_out);
+    HIPCHK(hipGetLastError());
     return RAE_OK;
 }

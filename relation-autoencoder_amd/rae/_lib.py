@@ -79,8 +79,16 @@ EXPORTS = (
     "rae_ipc_export", "rae_ipc_open", "rae_ipc_close", "rae_p2p_signals", "rae_set_peer",
     "rae_set_p2p_timeout", "rae_p2p_prologue",
     "rae_eval_workspace_bytes", "rae_eval_cost",
+    "rae_cluster_count", "rae_b3_metrics",
 )
 RAE_IPC_HANDLE_BYTES = 64
+# rae_cluster_count forms (include/rae.h RAE_CCOUNT_*)
+RAE_CCOUNT_AUTO = 0
+RAE_CCOUNT_LDS = 1
+RAE_CCOUNT_GLOBAL = 2
+RAE_CCOUNT_ACCUMULATE = 0x100
+RAE_CCOUNT_LDS_CELLS = 16384      # the LDS form's budget: relations * (n_gold + 1) counters
+CCOUNT_FORMS = {"auto": RAE_CCOUNT_AUTO, "lds": RAE_CCOUNT_LDS, "global": RAE_CCOUNT_GLOBAL}
 
 
 class RaeConfig(C.Structure):
@@ -211,6 +219,10 @@ def load(path: str | None = None):
     lib.rae_eval_workspace_bytes.restype = C.c_int64
     lib.rae_eval_cost.argtypes = [C.POINTER(RaeEvalArgs), _P]
     lib.rae_eval_cost.restype = C.c_int
+    lib.rae_cluster_count.argtypes = [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P]
+    lib.rae_cluster_count.restype = C.c_int
+    lib.rae_b3_metrics.argtypes = [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P]
+    lib.rae_b3_metrics.restype = C.c_int
     lib.rae_neg_sample.argtypes = [_P, C.c_int64, _P, C.c_int64, _P, _P]
     lib.rae_neg_sample_philox.argtypes = [_P, C.c_int64, C.c_uint64, C.c_uint64, C.c_int64, _P, _P]
     lib.rae_time_next.argtypes = [_P, _P, _P]

@@ -71,6 +71,10 @@ def get_command_args(argv=None, program_name="rae"):
                         "evaluated splits (train, or valid and test)")
     p.add_argument("--eval-seed", dest="eval_seed", type=int, default=None,
                    help="key of the fixed negatives the objective is scored against")
+    p.add_argument("--cluster-eval", dest="cluster_eval", choices=["host", "device"],
+                   default="host",
+                   help="where the induced clusters are scored: the host evaluator, or the "
+                        "contingency table and B^3 on the GPU")
     if argv is not None and len(argv) == 0:
         p.print_help()
         raise SystemExit(1)
@@ -125,7 +129,8 @@ def main(argv=None):
                              args.optimizer, args.model_name, args.decoder, args.ext_emb,
                              args.ext_reg, args.freq_eval, args.alpha, device=dev, world_size=ws,
                              rank=rk, exchange=exchange, graph_chunk=args.graph_chunk,
-                             eval_cost=args.eval_cost, eval_seed=args.eval_seed)
+                             eval_cost=args.eval_cost, eval_seed=args.eval_seed,
+                             cluster_eval=args.cluster_eval)
     if exchange is not None:
         ind.compile_function()
         rdist.warm_up(exchange, ind.engine.exchange_buf)

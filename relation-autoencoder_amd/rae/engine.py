@@ -32,6 +32,11 @@ _hip = None
 # TrainEngine.evaluate's result: cost = reconstruction + entropy (Python floats), the
 # (nrows, 3) terms tensor (or None) and the three double column sums (S_pos, S_H, S_neg)
 EvalResult = collections.namedtuple("EvalResult", "cost reconstruction entropy terms sums")
+# TrainEngine.cluster_metrics' result: B^3 f1 / precision / recall (Python floats), the number
+# of clustered elements (int), the cluster sizes (numpy int64, relations) and the
+# (relations, n_gold + 1) contingency table (numpy int64, or None when not asked for)
+ClusterResult = collections.namedtuple("ClusterResult",
+                                       "f1 precision recall n_elements sizes table")
 
 
 def _upload_graph(g, stream):
@@ -907,3 +912,85 @@ class TrainEngine:
         a.sums_out = p(self._eval_sums)
         a.workspace, a.workspace_bytes = p(self._eval_ws), int(self._eval_ws.numel())
         _lib.check(self.lib.rae_eval_cost(C.byref(a), self._stream()), "rae_eval_cost")
+
+    # ------------------------------------------------------------------ cluster evaluation
+    def _gold_dev(self, split: DeviceSplit, gold_index):
+        """The gold ids (int32, split.N; -1 past the index's rows) and sizes (int64) of
+        `gold_index` in HBM, uploaded once per (split, gold_index) like eval_negatives."""
+        cache = self.__dict__.setdefault("_gold_cache", {})
+        key = (id(split), id(gold_index))
+        hit = cache.get(key)
+        if hit is not None and hit[0] is split and hit[1] is gold_index:
+            return hit[2], hit[3]
+        ids = np.full(max(split.N, 1), -1, dtype=np.int32)
+        k = min(split.N, int(gold_index.ids.shape[0]))
+        ids[:k] = gold_index.ids[:k]
+        ids_d = torch.as_tensor(ids, device=self.device)
+        sizes_d = torch.as_tensor(np.ascontiguousarray(gold_index.sizes, dtype=np.int64),
+                                  device=self.device)
+        if sizes_d.numel() == 0:             # a pointer even for an empty gold standard
+            sizes_d = torch.zeros(1, dtype=torch.int64, device=self.device)
+        cache[key] = (split, gold_index, ids_d, sizes_d)
+        return ids_d, sizes_d
+
+    def queue_cluster_metrics(self, split: DeviceSplit, gold_index, row0: int = 0,
+                              nrows: int | None = None, form: str = "auto"):
+        """Queue rae_label(probs=None) -> rae_cluster_count -> rae_b3_metrics for rows
+        [row0, row0+nrows) of `split` on the current stream (no host synchronisation, no
+        allocation after the first call of a shape: capturable).  The table lands in
+        self._cl_table[:relations * (n_gold + 1)], the four metric doubles and the cluster sizes
+        in self._cl_out (int64 words: [0:4] the doubles' bits, [4:4+relations] the sizes).
+        cluster_metrics() is this plus the read-back; tools/cluster_eval_bench.py times it."""
+        if form not in _lib.CCOUNT_FORMS:
+            raise ValueError(f"form must be one of {sorted(_lib.CCOUNT_FORMS)}")
+        row0 = int(row0)
+        nrows = split.N - row0 if nrows is None else int(nrows)
+        if row0 < 0 or nrows < 0 or row0 + nrows > split.N:
+            raise IndexError(f"rows [{row0}, {row0 + nrows}) out of the split's {split.N}")
+        ng = int(gold_index.n_gold)
+        ids_d, sizes_d = self._gold_dev(split, gold_index)
+        cells = self.m * (ng + 1)
+        if getattr(self, "_cl_out", None) is None:       # once per engine
+            self._cl_out = torch.zeros(4 + self.m, dtype=torch.int64, device=self.device)
+            self._cl_table = None
+            self._cl_labels = None
+        if self._cl_table is None or self._cl_table.numel() < cells:
+            self._cl_table = torch.zeros(cells, dtype=torch.int64, device=self.device)
+        if self._cl_labels is None or self._cl_labels.numel() < nrows:
+            self._cl_labels = torch.empty(max(nrows, 1), dtype=torch.int64, device=self.device)
+        st = self._stream()
+        W, Wb = self.model.params[0], self.model.params[1]
+        lab = self._cl_labels
+        _lib.check(self.lib.rae_label(
+            C.c_void_p(split.indptr.data_ptr()), C.c_void_p(split.indices.data_ptr()),
+            C.c_void_p(split.values.data_ptr()) if split.values is not None else None,
+            C.c_void_p(W.data_ptr()), C.c_void_p(Wb.data_ptr()), self.m, row0, nrows,
+            C.c_void_p(lab.data_ptr()), None, st), "rae_label")
+        _lib.check(self.lib.rae_cluster_count(
+            C.c_void_p(lab.data_ptr()), C.c_void_p(ids_d.data_ptr() + 4 * row0), nrows, self.m,
+            ng, _lib.CCOUNT_FORMS[form], C.c_void_p(self._cl_table.data_ptr()), st),
+            "rae_cluster_count")
+        _lib.check(self.lib.rae_b3_metrics(
+            C.c_void_p(self._cl_table.data_ptr()), C.c_void_p(sizes_d.data_ptr()),
+            int(gold_index.n_assessable), self.m, ng, C.c_void_p(self._cl_out.data_ptr()),
+            C.c_void_p(self._cl_out.data_ptr() + 32), st), "rae_b3_metrics")
+
+    def cluster_metrics(self, split: DeviceSplit, gold_index, row0: int = 0,
+                        nrows: int | None = None, table: bool = False, form: str = "auto"):
+        """B^3 of the induced clusters of rows [row0, row0+nrows) of `split` at the current
+        W / Wb against `gold_index` (rae.evaluation.GoldIndex), all on the device:
+        ClusterResult(f1, precision, recall, n_elements, sizes, table) with compute_metrics'
+        values (rae.evaluation.b3_from_table is the host oracle), sizes the cluster sizes
+        (get_clusters_size) and, table=True, the contingency table.  One read-back (the four
+        doubles and the sizes; the table only when asked).  Touches no training state.
+        Partitioned update with stale rows: gathers W first (a collective, like label)."""
+        if self.stale(accumulators=False):
+            self.sync_replicas(accumulators=False)
+        self.queue_cluster_metrics(split, gold_index, row0, nrows, form)
+        ng = int(gold_index.n_gold)
+        host = self._cl_out.cpu().numpy()
+        f1, pre, rec, nel = (float(x) for x in host[:4].view(np.float64))
+        tb = None
+        if table:
+            tb = self._cl_table[:self.m * (ng + 1)].cpu().numpy().reshape(self.m, ng + 1)
+        return ClusterResult(f1, pre, rec, int(nel), host[4:].copy(), tb)

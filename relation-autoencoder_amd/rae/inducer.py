@@ -13,7 +13,7 @@ import torch
 
 from .data import SPLIT_LABELS
 from .engine import DeviceSplit, TrainEngine
-from .evaluation import construct_split_evaluator
+from .evaluation import GoldIndex, construct_split_evaluator
 from .model import OieModelFunctions, _as_bool, make_optimizer
 from .negatives import NegativeExampleGenerator
 
@@ -74,7 +74,9 @@ class ReconstructInducer:
                  graph_chunk=64, neg_sampler="device", neg_seed=0, mfma_bf16=False,
                  kernel_forms=None, dp_update="replicated", index_window=0,
                  index_overlap=True, p2p_cross_device=False, p2p_timeout=5.0,
-                 eval_cost=False, eval_seed=None):
+                 eval_cost=False, eval_seed=None, cluster_eval="host"):
+        if cluster_eval not in ("host", "device"):
+            raise ValueError("cluster_eval must be 'host' or 'device'")
         self.data = data
         self.goldStandard = gold_standard
         self.rng = rng
@@ -117,6 +119,12 @@ class ReconstructInducer:
         self.eval_cost = bool(eval_cost)
         self.eval_seed = eval_seed
         self.eval_costs = {s: [] for s in SPLIT_LABELS}
+        # cluster_eval: where learn() scores the induced clusters -- "host": the label download
+        # and the Python sets of the reference (get_clusters_sets + SingleLabelClusterEvaluation);
+        # "device": the contingency table and B^3 on the GPU (TrainEngine.cluster_metrics), same
+        # rows, same printed lines; self.cluster[split] is then not built
+        self.cluster_eval = cluster_eval
+        self._gold_index = {}
         self.negativeSampler = NegativeExampleGenerator(rng, data.negSamplingCum)   # :85
         self.modelID = (f"{decoder_model}_{model_name}_maxepoch{nb_epochs}_lr{learning_rate}"
                         f"_embedsize{embed_size}_l1{lambda1}_l2{lambda2}_opt{optimization}"
@@ -251,8 +259,7 @@ class ReconstructInducer:
                     else:                       # mode 2: valid + test after every batch
                         print(b * self.batch_size, b, "#" * 60)
                         for split in SPLIT_LABELS[1:]:
-                            self.cluster[split] = self.get_clusters_sets(split)
-                            self._evaluate(split, verbose=verbose)
+                            self._score(split, verbose=verbose)
             else:
                 self.engine.run(0, nb)
             costs = self.engine.costs[:nb].double().cpu().numpy()
@@ -267,12 +274,10 @@ class ReconstructInducer:
                 print("Training error: {:.4f}".format(err))
                 print("Epoch duration: {:.1f}s".format(time.perf_counter() - t0))
             if self._mode() == 1:
-                self.cluster["train"] = self.get_clusters_sets("train")
-                self._evaluate("train", verbose=verbose)
+                self._score("train", verbose=verbose)
             else:
                 for split in SPLIT_LABELS[1:]:
-                    self.cluster[split] = self.get_clusters_sets(split)
-                    self._evaluate(split, verbose=verbose)
+                    self._score(split, verbose=verbose)
             if self.eval_cost:
                 for split in (SPLIT_LABELS[:1] if self._mode() == 1 else SPLIT_LABELS[1:]):
                     self.evaluate_cost(split, verbose=verbose)
@@ -304,14 +309,41 @@ class ReconstructInducer:
 
     def get_clusters_size(self, split="train"):
         """get_clusters_size (OieInduction.py:248-259)."""
+        if self.cluster_eval == "device":
+            sizes = self._cluster_result(split).sizes
+            return Counter({c: int(n) for c, n in enumerate(sizes) if n})
         return Counter(int(x) for x in self._labels(split))
+
+    def _cluster_result(self, split):
+        """cluster_eval="device": TrainEngine.cluster_metrics over the rows _labels covers (the
+        first nbs * batch_size), against the split's whole gold standard."""
+        if not self._check_for_compiled_functions():
+            self.compile_function()
+        ds = self._dev_split[split]
+        gi = self._gold_index.get(split)
+        if gi is None:
+            gi = self._gold_index[split] = GoldIndex(
+                (self.goldStandard or {}).get(split, {}), ds.N)
+        nbs = self.data.split[split].args1.shape[0] // self.batch_size
+        return self.engine.cluster_metrics(ds, gi, 0, nbs * self.batch_size)
+
+    def _score(self, split, verbose=True):
+        """learn()'s evaluation of one split: the cluster sets and the host evaluator, or
+        (cluster_eval="device") the device metrics."""
+        if self.cluster_eval == "host":
+            self.cluster[split] = self.get_clusters_sets(split)
+        return self._evaluate(split, verbose=verbose)
 
     def _evaluate(self, split, verbose=True):
         ev = self.evaluator.get(split)
         if ev is None:
             return None
-        ev.feed_induced_clusters(self.cluster[split])
-        f1, pre, rec = ev.compute_metrics()
+        if self.cluster_eval == "device":
+            res = self._cluster_result(split)
+            f1, pre, rec = res.f1, res.precision, res.recall
+        else:
+            ev.feed_induced_clusters(self.cluster[split])
+            f1, pre, rec = ev.compute_metrics()
         if verbose:
             print("{} f1: {:.4f} pre: {:.4f} rec: {:.4f}".format(split, f1, pre, rec))
         return f1, pre, rec
