@@ -407,6 +407,41 @@ int rae_b3_metrics(const int64_t* table, const int64_t* gold_sizes, int64_t n_as
                    int32_t relations, int32_t n_gold, double* metrics_out,
                    int64_t* sizes_out, rae_stream_t stream);
 
+/* --- per-cluster trigger profiles (Visualizator.print_clusters evaluation/Visuals.py:8-45;
+ *     get_example_feature learning/OieData.py:100-106) ------------------------------------ */
+/* Plan-free and stream-ordered like the cluster evaluation above: every pointer is a device
+ * pointer, no allocation, no synchronisation (capturable), arguments checked before the first
+ * HIP call, integer arithmetic only (bit-exact whatever the grid or arrival order).        */
+
+/* keys_out[i] = key_of_feature[f], f the first stored column of row row0 + i (CSR order) with
+ * key_of_feature[f] >= 0; -1 when the row has none.  values != NULL: a column whose stored
+ * value is 0 is not counted (scipy's nonzero() drops it in the reference).  A column index
+ * outside [0, n_features) carries no key (never an out-of-range read).  n_features and nrows in
+ * [0, 2^31); nrows == 0 is valid.  Computed once per split: the key is static.             */
+int rae_row_keys(const int32_t* indptr, const int32_t* indices, const float* values,
+                 const int32_t* key_of_feature, int64_t n_features,
+                 int64_t row0, int64_t nrows, int32_t* keys_out, rae_stream_t stream);
+
+/* counts[c * n_keys + k] += |{ i < nrows : labels[i] == c, keys[i] == k }|; rows with a label
+ * outside [0, relations) or a key outside [0, n_keys) are skipped (there is no "unlabelled"
+ * column: the reference drops None).  The table is zeroed by a kernel first unless
+ * accumulate != 0.  relations in [1, 512], n_keys in [1, 2^22], relations * n_keys <= 2^27
+ * (512 MiB of counters), 0 <= nrows < 2^31: a cell cannot overflow within one call, and a
+ * caller who accumulates keeps the total number of rows below 2^31.  labels / keys need their
+ * element alignment only (16-byte reads between a scalar head and tail).  32-bit integer
+ * atomics into global memory; the duplicates of a wave instruction are merged first.       */
+int rae_cluster_key_count(const int64_t* labels, const int32_t* keys, int64_t nrows,
+                          int32_t relations, int32_t n_keys, int32_t accumulate,
+                          int32_t* counts, rae_stream_t stream);
+
+/* Row c of the table starts at counts + c * ld (ld >= n_keys); keys_out / counts_out are
+ * (relations, top) int32.  A row's output is its cells with count > 0 ordered by count
+ * descending, then key ascending (a total order: the output is unique), cut to `top` entries
+ * and padded with (-1, 0).  top in [1, 32] (top > n_keys is valid), n_keys in [1, 2^22]; counts
+ * up to 2^31 - 1 order correctly.  One pass over each row.                                  */
+int rae_cluster_topk(const int32_t* counts, int32_t relations, int32_t n_keys, int64_t ld,
+                     int32_t top, int32_t* keys_out, int32_t* counts_out, rae_stream_t stream);
+
 /* --- measurement helper (bench.py; no reference counterpart) ------------------------- */
 /* STREAM-style device copy of `bytes` (multiple of 16, 16-byte aligned pointers) with float4
  * loads and stores: the measured HBM ceiling bench.py reports next to the 8 TB/s spec.   */

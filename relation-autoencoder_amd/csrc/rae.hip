@@ -33,6 +33,7 @@
 #include "rae_index.hpp"
 #include "rae_label.hpp"
 #include "rae_p2p.hpp"
+#include "rae_profile.hpp"
 #include "rae_sampler.hpp"
 #include "rae_sp.hpp"
 #include "rae_step.hpp"
@@ -1542,6 +1543,96 @@ extern "C" int rae_b3_metrics(const int64_t* table, const int64_t* gold_sizes, i
                        (const long long*)table, (const long long*)gold_sizes,
                        (long long)n_assessable, (int)relations, (int)n_gold, metrics_out,
                        (long long*)sizes_out);
+    HIPCHK(hipGetLastError());
+    return RAE_OK;
+}
+
+// ---- per-cluster trigger profiles -----------------------------------------------------------
+extern "C" int rae_row_keys(const int32_t* indptr, const int32_t* indices, const float* values,
+                            const int32_t* key_of_feature, int64_t n_features, int64_t row0,
+                            int64_t nrows, int32_t* keys_out, rae_stream_t stream) {
+    if (!indptr) return fail(RAE_E_INVALID, "indptr is NULL");
+    if (!indices) return fail(RAE_E_INVALID, "indices is NULL");
+    if (!key_of_feature) return fail(RAE_E_INVALID, "key_of_feature is NULL");
+    if (!keys_out) return fail(RAE_E_INVALID, "keys_out is NULL");
+    if (n_features < 0 || n_features >= (1ll << 31))
+        return fail(RAE_E_INVALID, "n_features must be in [0, 2^31)");
+    if (row0 < 0) return fail(RAE_E_INVALID, "row0 must be >= 0");
+    if (nrows < 0 || nrows >= (1ll << 31)) return fail(RAE_E_INVALID, "nrows must be in [0, 2^31)");
+    if (((uintptr_t)indptr & 3) || ((uintptr_t)indices & 3) || ((uintptr_t)values & 3) ||
+        ((uintptr_t)key_of_feature & 3) || ((uintptr_t)keys_out & 3))
+        return fail(RAE_E_INVALID, "pointers must be 4-byte aligned");
+    if (nrows == 0) return RAE_OK;
+    const int64_t per = 4 * (RAE_RK_BT / 64);             // rows per workgroup and round
+    const int64_t grid = std::min<int64_t>((nrows + per - 1) / per, 65536);
+    hipLaunchKernelGGL(k_row_keys, dim3((unsigned)grid), dim3(RAE_RK_BT), 0, (hipStream_t)stream,
+                       indptr, indices, values, key_of_feature, (long long)n_features,
+                       (long long)row0, (long long)nrows, keys_out);
+    HIPCHK(hipGetLastError());
+    return RAE_OK;
+}
+
+extern "C" int rae_cluster_key_count(const int64_t* labels, const int32_t* keys, int64_t nrows,
+                                     int32_t relations, int32_t n_keys, int32_t accumulate,
+                                     int32_t* counts, rae_stream_t stream) {
+    if (!labels) return fail(RAE_E_INVALID, "labels is NULL");
+    if (!keys) return fail(RAE_E_INVALID, "keys is NULL");
+    if (!counts) return fail(RAE_E_INVALID, "counts is NULL");
+    if (relations < 1 || relations > 512)
+        return fail(RAE_E_INVALID, "relations must be in [1, 512]");
+    if (n_keys < 1 || n_keys > (1 << 22)) return fail(RAE_E_INVALID, "n_keys must be in [1, 2^22]");
+    const int64_t cells = (int64_t)relations * n_keys;
+    if (cells > (1ll << 27)) return fail(RAE_E_INVALID, "relations * n_keys must be <= 2^27");
+    if (nrows < 0 || nrows >= (1ll << 31)) return fail(RAE_E_INVALID, "nrows must be in [0, 2^31)");
+    if (((uintptr_t)labels & 7) || ((uintptr_t)keys & 3) || ((uintptr_t)counts & 3))
+        return fail(RAE_E_INVALID, "labels / keys / counts must be aligned to their element size");
+    hipStream_t st = (hipStream_t)stream;
+    unsigned* ct = (unsigned*)counts;
+    if (!accumulate) {
+        const int64_t zg = std::min<int64_t>((cells + 255) / 256, 4096);
+        hipLaunchKernelGGL(k_ck_zero, dim3((unsigned)zg), dim3(256), 0, st, ct, (long long)cells);
+        HIPCHK(hipGetLastError());
+    }
+    if (nrows == 0) return RAE_OK;
+    // rows before the first index at which both pointers are 16-byte aligned (GV); with none,
+    // the labels alone are aligned and the keys are read as dwords
+    int head = -1;
+    for (int h = 0; h < 4; ++h)
+        if ((((uintptr_t)(labels + h)) & 15) == 0 && (((uintptr_t)(keys + h)) & 15) == 0) {
+            head = h;
+            break;
+        }
+    const bool gv = head >= 0;
+    if (!gv) head = ((uintptr_t)labels & 15) ? 1 : 0;
+    if (head > nrows) head = (int)nrows;
+    const int64_t nq = (nrows - head) >> 2;
+    const int64_t per = (int64_t)RAE_CK_BT * RAE_CK_QPT;
+    const int64_t grid = std::max<int64_t>(1, std::min<int64_t>((nq + per - 1) / per, RAE_CK_GRID));
+    with_bool(gv, [&](auto Gf) {
+        hipLaunchKernelGGL((k_ckcount<RAE_CV(Gf)>), dim3((unsigned)grid), dim3(RAE_CK_BT), 0, st,
+                           (const long long*)labels, (const int*)keys, (long long)nrows, head,
+                           (int)relations, (int)n_keys, ct);
+    });
+    HIPCHK(hipGetLastError());
+    return RAE_OK;
+}
+
+extern "C" int rae_cluster_topk(const int32_t* counts, int32_t relations, int32_t n_keys,
+                                int64_t ld, int32_t top, int32_t* keys_out, int32_t* counts_out,
+                                rae_stream_t stream) {
+    if (!counts) return fail(RAE_E_INVALID, "counts is NULL");
+    if (!keys_out) return fail(RAE_E_INVALID, "keys_out is NULL");
+    if (!counts_out) return fail(RAE_E_INVALID, "counts_out is NULL");
+    if (relations < 1 || relations > 512)
+        return fail(RAE_E_INVALID, "relations must be in [1, 512]");
+    if (n_keys < 1 || n_keys > (1 << 22)) return fail(RAE_E_INVALID, "n_keys must be in [1, 2^22]");
+    if (ld < n_keys) return fail(RAE_E_INVALID, "ld must be >= n_keys");
+    if (top < 1 || top > RAE_TK_MAXTOP) return fail(RAE_E_INVALID, "top must be in [1, 32]");
+    if (((uintptr_t)counts & 3) || ((uintptr_t)keys_out & 3) || ((uintptr_t)counts_out & 3))
+        return fail(RAE_E_INVALID, "counts / keys_out / counts_out must be 4-byte aligned");
+    hipLaunchKernelGGL(k_ctopk, dim3((unsigned)relations), dim3(RAE_TK_BT), 0, (hipStream_t)stream,
+                       (const int*)counts, (int)n_keys, (long long)ld, (int)top, keys_out,
+                       counts_out);
     HIPCHK(hipGetLastError());
     return RAE_OK;
 }

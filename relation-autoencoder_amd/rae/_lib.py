@@ -80,6 +80,7 @@ EXPORTS = (
     "rae_set_p2p_timeout", "rae_p2p_prologue",
     "rae_eval_workspace_bytes", "rae_eval_cost",
     "rae_cluster_count", "rae_b3_metrics",
+    "rae_row_keys", "rae_cluster_key_count", "rae_cluster_topk",
 )
 RAE_IPC_HANDLE_BYTES = 64
 # rae_cluster_count forms (include/rae.h RAE_CCOUNT_*)
@@ -88,6 +89,12 @@ RAE_CCOUNT_LDS = 1
 RAE_CCOUNT_GLOBAL = 2
 RAE_CCOUNT_ACCUMULATE = 0x100
 RAE_CCOUNT_LDS_CELLS = 16384      # the LDS form's budget: relations * (n_gold + 1) counters
+# rae_cluster_key_count / rae_cluster_topk limits (include/rae.h) and the kernels' grid constants
+# (csrc/rae_profile.hpp RAE_CK_*)
+RAE_KEYCOUNT_MAX_KEYS = 1 << 22
+RAE_KEYCOUNT_MAX_CELLS = 1 << 27
+RAE_TOPK_MAX = 32
+RAE_CK_BT, RAE_CK_QPT, RAE_CK_GRID = 256, 4, 2048
 CCOUNT_FORMS = {"auto": RAE_CCOUNT_AUTO, "lds": RAE_CCOUNT_LDS, "global": RAE_CCOUNT_GLOBAL}
 
 
@@ -223,6 +230,12 @@ def load(path: str | None = None):
     lib.rae_cluster_count.restype = C.c_int
     lib.rae_b3_metrics.argtypes = [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P]
     lib.rae_b3_metrics.restype = C.c_int
+    lib.rae_row_keys.argtypes = [_P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P]
+    lib.rae_row_keys.restype = C.c_int
+    lib.rae_cluster_key_count.argtypes = [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P]
+    lib.rae_cluster_key_count.restype = C.c_int
+    lib.rae_cluster_topk.argtypes = [_P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _P, _P, _P]
+    lib.rae_cluster_topk.restype = C.c_int
     lib.rae_neg_sample.argtypes = [_P, C.c_int64, _P, C.c_int64, _P, _P]
     lib.rae_neg_sample_philox.argtypes = [_P, C.c_int64, C.c_uint64, C.c_uint64, C.c_int64, _P, _P]
     lib.rae_time_next.argtypes = [_P, _P, _P]

@@ -75,6 +75,17 @@ def get_command_args(argv=None, program_name="rae"):
                    default="host",
                    help="where the induced clusters are scored: the host evaluator, or the "
                         "contingency table and B^3 on the GPU")
+    p.add_argument("--print-clusters", dest="print_clusters", choices=["off", "host", "device"],
+                   default="off",
+                   help="after each evaluation print every induced relation's most frequent "
+                        "triggers with their frequencies: from downloaded labels on the host, "
+                        "or by the key table and top-k kernels on the GPU")
+    p.add_argument("--print-top", dest="print_top", type=int, default=5,
+                   help="triggers printed per relation (1..32)")
+    p.add_argument("--print-clusters-by", dest="print_by", choices=["trigger", "gold"],
+                   default="trigger",
+                   help="what is counted per relation: the examples' triggers (needs a dataset "
+                        "written by rae.preprocess) or their first gold labels")
     if argv is not None and len(argv) == 0:
         p.print_help()
         raise SystemExit(1)
@@ -130,7 +141,9 @@ def main(argv=None):
                              args.ext_reg, args.freq_eval, args.alpha, device=dev, world_size=ws,
                              rank=rk, exchange=exchange, graph_chunk=args.graph_chunk,
                              eval_cost=args.eval_cost, eval_seed=args.eval_seed,
-                             cluster_eval=args.cluster_eval)
+                             cluster_eval=args.cluster_eval,
+                             print_clusters=args.print_clusters, print_top=args.print_top,
+                             print_by=args.print_by)
     if exchange is not None:
         ind.compile_function()
         rdist.warm_up(exchange, ind.engine.exchange_buf)

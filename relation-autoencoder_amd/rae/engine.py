@@ -37,6 +37,9 @@ EvalResult = collections.namedtuple("EvalResult", "cost reconstruction entropy t
 # (relations, n_gold + 1) contingency table (numpy int64, or None when not asked for)
 ClusterResult = collections.namedtuple("ClusterResult",
                                        "f1 precision recall n_elements sizes table")
+# TrainEngine.cluster_profiles' result: per cluster the `top` most frequent keys and their counts,
+# both (relations, top) numpy int32, padded with (-1, 0) (rae.evaluation.topk_from_table's order)
+ProfileResult = collections.namedtuple("ProfileResult", "keys counts")
 
 
 def _upload_graph(g, stream):
@@ -443,6 +446,7 @@ class TrainEngine:
         b = int(batch_index)
         if not 0 <= b < self.nb:
             raise IndexError(f"batch index {b} out of range [0, {self.nb})")
+        self._cl_labels_of = None        # labels of the old parameters are not reused
         self._new_negatives()            # its index slot is rebuilt with the call's negatives
         self.call_neg[0].copy_(torch.from_numpy(n1))
         self.call_neg[1].copy_(torch.from_numpy(n2))
@@ -642,6 +646,7 @@ class TrainEngine:
         peer-to-peer exchange only): a host barrier of the ranks first -- a caller that has
         just met its peers (bench.py's timed region) may skip it."""
         self._ensure_epoch_mode()
+        self._cl_labels_of = None        # labels of the old parameters are not reused
         if self._dp:
             self._stale.update(("params", "acc"))
         if self._p2p and sync_peers:
@@ -966,6 +971,7 @@ class TrainEngine:
             C.c_void_p(split.values.data_ptr()) if split.values is not None else None,
             C.c_void_p(W.data_ptr()), C.c_void_p(Wb.data_ptr()), self.m, row0, nrows,
             C.c_void_p(lab.data_ptr()), None, st), "rae_label")
+        self._cl_labels_of = (id(split), row0, nrows)    # queue_cluster_profiles(reuse_labels)
         _lib.check(self.lib.rae_cluster_count(
             C.c_void_p(lab.data_ptr()), C.c_void_p(ids_d.data_ptr() + 4 * row0), nrows, self.m,
             ng, _lib.CCOUNT_FORMS[form], C.c_void_p(self._cl_table.data_ptr()), st),
@@ -987,6 +993,7 @@ class TrainEngine:
         if self.stale(accumulators=False):
             self.sync_replicas(accumulators=False)
         self.queue_cluster_metrics(split, gold_index, row0, nrows, form)
+        self._cl_labels_of = None        # the queued sequence ends here: no later reuse
         ng = int(gold_index.n_gold)
         host = self._cl_out.cpu().numpy()
         f1, pre, rec, nel = (float(x) for x in host[:4].view(np.float64))
@@ -994,3 +1001,125 @@ class TrainEngine:
         if table:
             tb = self._cl_table[:self.m * (ng + 1)].cpu().numpy().reshape(self.m, ng + 1)
         return ClusterResult(f1, pre, rec, int(nel), host[4:].copy(), tb)
+
+    # ------------------------------------------------------------------ cluster profiles
+    def _keys_dev(self, split: DeviceSplit, key_index):
+        """The key of every row of `split` (int32, split.N) under `key_index`
+        (rae.evaluation.KeyIndex) in HBM: rae_row_keys over the whole split, or the upload of
+        the index's own per-row keys (from_gold; -1 past them) -- once per (split, key_index),
+        cached like _gold_dev: an example's key is static."""
+        cache = self.__dict__.setdefault("_key_cache", {})
+        key = (id(split), id(key_index))
+        hit = cache.get(key)
+        if hit is not None and hit[0] is split and hit[1] is key_index:
+            return hit[2]
+        if key_index.rows is not None:
+            rows = np.full(max(split.N, 1), -1, dtype=np.int32)
+            k = min(split.N, int(key_index.rows.shape[0]))
+            rows[:k] = key_index.rows[:k]
+            keys_d = torch.as_tensor(rows, device=self.device)
+        else:
+            kof = key_index.key_of_feature
+            if kof.shape[0] != split.d:
+                raise ValueError(f"key index over {kof.shape[0]} features, split has {split.d}")
+            kof_d = torch.as_tensor(kof, device=self.device)
+            keys_d = torch.empty(max(split.N, 1), dtype=torch.int32, device=self.device)
+            _lib.check(self.lib.rae_row_keys(
+                C.c_void_p(split.indptr.data_ptr()), C.c_void_p(split.indices.data_ptr()),
+                C.c_void_p(split.values.data_ptr()) if split.values is not None else None,
+                C.c_void_p(kof_d.data_ptr()), split.d, 0, split.N,
+                C.c_void_p(keys_d.data_ptr()), self._stream()), "rae_row_keys")
+        cache[key] = (split, key_index, keys_d)
+        return keys_d
+
+    def queue_cluster_profiles(self, split: DeviceSplit, key_index, row0: int = 0,
+                               nrows: int | None = None, top: int = 5,
+                               reuse_labels: bool = False):
+        """Queue rae_label(probs=None) -> rae_cluster_key_count -> rae_cluster_topk for rows
+        [row0, row0+nrows) of `split` on the current stream (no host synchronisation; no
+        allocation after the first call of a shape, the split's row keys included: capturable
+        from the second call on).  The table lands in self._pf_table[:relations * n_keys], the
+        result in self._pf_out (int32 words: [0 : relations * top] the keys, [relations * 32 :
+        relations * 32 + relations * top] the counts).  reuse_labels: skip the labelling pass
+        and count the labels queue_cluster_metrics queued just before for the same rows -- in
+        one queued sequence only (the mark is consumed here and dropped by every training step:
+        labels are never reused across a parameter update)."""
+        row0 = int(row0)
+        nrows = split.N - row0 if nrows is None else int(nrows)
+        top = int(top)
+        if row0 < 0 or nrows < 0 or row0 + nrows > split.N:
+            raise IndexError(f"rows [{row0}, {row0 + nrows}) out of the split's {split.N}")
+        if not 1 <= top <= _lib.RAE_TOPK_MAX:
+            raise ValueError(f"top must be in [1, {_lib.RAE_TOPK_MAX}]")
+        nk = int(key_index.n_keys)
+        if nk < 1:
+            raise ValueError("the key index has no keys")
+        keys_d = self._keys_dev(split, key_index)
+        cells = self.m * nk
+        if getattr(self, "_pf_out", None) is None:       # once per engine
+            self._pf_out = torch.zeros(2 * self.m * _lib.RAE_TOPK_MAX, dtype=torch.int32,
+                                       device=self.device)
+            self._pf_table = None
+        if self._pf_table is None or self._pf_table.numel() < cells:
+            self._pf_table = torch.zeros(cells, dtype=torch.int32, device=self.device)
+        st = self._stream()
+        mark = (id(split), row0, nrows)
+        if reuse_labels:
+            if getattr(self, "_cl_labels_of", None) != mark:
+                raise RuntimeError("reuse_labels: queue_cluster_metrics was not queued for these "
+                                   "rows just before")
+        else:
+            if getattr(self, "_cl_labels", None) is None or self._cl_labels.numel() < nrows:
+                self._cl_labels = torch.empty(max(nrows, 1), dtype=torch.int64,
+                                              device=self.device)
+            W, Wb = self.model.params[0], self.model.params[1]
+            _lib.check(self.lib.rae_label(
+                C.c_void_p(split.indptr.data_ptr()), C.c_void_p(split.indices.data_ptr()),
+                C.c_void_p(split.values.data_ptr()) if split.values is not None else None,
+                C.c_void_p(W.data_ptr()), C.c_void_p(Wb.data_ptr()), self.m, row0, nrows,
+                C.c_void_p(self._cl_labels.data_ptr()), None, st), "rae_label")
+        self._cl_labels_of = None
+        _lib.check(self.lib.rae_cluster_key_count(
+            C.c_void_p(self._cl_labels.data_ptr()), C.c_void_p(keys_d.data_ptr() + 4 * row0),
+            nrows, self.m, nk, 0, C.c_void_p(self._pf_table.data_ptr()), st),
+            "rae_cluster_key_count")
+        half = self.m * _lib.RAE_TOPK_MAX
+        _lib.check(self.lib.rae_cluster_topk(
+            C.c_void_p(self._pf_table.data_ptr()), self.m, nk, nk, top,
+            C.c_void_p(self._pf_out.data_ptr()), C.c_void_p(self._pf_out.data_ptr() + 4 * half),
+            st), "rae_cluster_topk")
+
+    def _profile_result(self, top: int):
+        host = self._pf_out.cpu().numpy()
+        half, n = self.m * _lib.RAE_TOPK_MAX, self.m * top
+        return ProfileResult(host[:n].reshape(self.m, top).copy(),
+                             host[half:half + n].reshape(self.m, top).copy())
+
+    def cluster_profiles(self, split: DeviceSplit, key_index, row0: int = 0,
+                         nrows: int | None = None, top: int = 5):
+        """Per induced cluster the `top` most frequent keys (triggers, or gold labels) of rows
+        [row0, row0+nrows) of `split` at the current W / Wb, all on the device:
+        ProfileResult(keys, counts), both (relations, top) int32 -- count descending, then key
+        ascending, padded with (-1, 0); rae.evaluation.key_table + topk_from_table over the
+        downloaded labels is the host oracle.  One read-back of 2 * relations * 32 words.
+        Touches no training state.  Partitioned update with stale rows: gathers W first (a
+        collective, like label)."""
+        if self.stale(accumulators=False):
+            self.sync_replicas(accumulators=False)
+        self.queue_cluster_profiles(split, key_index, row0, nrows, top)
+        return self._profile_result(int(top))
+
+    def cluster_metrics_and_profiles(self, split: DeviceSplit, gold_index, key_index,
+                                     row0: int = 0, nrows: int | None = None, top: int = 5,
+                                     form: str = "auto"):
+        """cluster_metrics and cluster_profiles of the same rows from ONE labelling pass:
+        label -> count -> b3 -> key count -> top-k queued back to back, then the two
+        read-backs.  Returns (ClusterResult, ProfileResult)."""
+        if self.stale(accumulators=False):
+            self.sync_replicas(accumulators=False)
+        self.queue_cluster_metrics(split, gold_index, row0, nrows, form)
+        self.queue_cluster_profiles(split, key_index, row0, nrows, top, reuse_labels=True)
+        host = self._cl_out.cpu().numpy()
+        f1, pre, rec, nel = (float(x) for x in host[:4].view(np.float64))
+        return (ClusterResult(f1, pre, rec, int(nel), host[4:].copy(), None),
+                self._profile_result(int(top)))

@@ -10,6 +10,10 @@ per-element set intersections, without its O(|A| * |C|) set work).
 GoldIndex / contingency_table / b3_from_table are the array form of the same computation: the
 gold standard as an id vector, the table by bincount, the metrics from the table.  They are the
 host oracle of the device path (rae_cluster_count / rae_b3_metrics, TrainEngine.cluster_metrics).
+
+KeyIndex / row_keys / key_table / topk_from_table / format_cluster_profiles do the same for the
+per-cluster profiles (rae_row_keys / rae_cluster_key_count / rae_cluster_topk,
+TrainEngine.cluster_profiles).
 """
 from __future__ import annotations
 
@@ -152,3 +156,141 @@ def b3_from_table(table, sizes, n_assessable):
     if rec == 0.0 and pre == 0.0:
         return 0.0, pre, rec
     return (2 * rec * pre) / (rec + pre), pre, rec
+
+
+# ---------------------------------------------------------------------------------------------
+# per-cluster profiles (Visualizator.print_clusters, evaluation/Visuals.py:8-45): for every
+# induced relation the most frequent triggers (or gold labels) of its members
+# ---------------------------------------------------------------------------------------------
+class KeyIndex:
+    """What print_clusters counts, as arrays (the analogue of GoldIndex):
+    key_of_feature  int32, length d: the key a feature carries, -1 for none -- an example's key
+                    is that of its first keyed stored column (get_example_feature,
+                    learning/OieData.py:100-106); None for an index made by from_gold;
+    names           the keys' display strings (key k prints as names[k]);
+    rows            None, or (from_gold) the per-row keys themselves, int32."""
+
+    def __init__(self, key_of_feature, names, rows=None):
+        self.key_of_feature = None if key_of_feature is None else \
+            np.ascontiguousarray(key_of_feature, dtype=np.int32)
+        self.names = list(names)
+        self.rows = None if rows is None else np.ascontiguousarray(rows, dtype=np.int32)
+
+    @property
+    def n_keys(self):
+        return len(self.names)
+
+    @classmethod
+    def from_lexicon(cls, lex, token="trigger"):
+        """The reference's rule: a feature carries a key iff its pruned string s has
+        s.find(token) > -1 (OieData.py:104); it displays as s.replace(token + '#', '')
+        (Visuals.py:64).  Features with equal display strings share a key (the reference's
+        Counter counts strings); keys are numbered by the smallest feature id carrying them."""
+        d = int(lex.get_feature_space_dimensionality())
+        kof = np.full(d, -1, dtype=np.int32)
+        names, key_of_name = [], {}
+        for f in range(d):
+            s = lex.get_str_pruned(f)
+            if s is None or s.find(token) < 0:
+                continue
+            name = s.replace(token + "#", "")
+            k = key_of_name.get(name)
+            if k is None:
+                k = key_of_name[name] = len(names)
+                names.append(name)
+            kof[f] = k
+        return cls(kof, names)
+
+    @classmethod
+    def from_mask(cls, mask, names=None):
+        """Every feature with mask[f] set is a key of its own, numbered in feature order;
+        names default to the feature ids as strings."""
+        mask = np.asarray(mask, dtype=bool)
+        feats = np.flatnonzero(mask)
+        kof = np.full(mask.shape[0], -1, dtype=np.int32)
+        kof[feats] = np.arange(feats.shape[0], dtype=np.int32)
+        if names is None:
+            names = [str(int(f)) for f in feats]
+        if len(names) != feats.shape[0]:
+            raise ValueError(f"{len(names)} names for {feats.shape[0]} keyed features")
+        return cls(kof, names)
+
+    @classmethod
+    def from_gold(cls, gold_split, n_rows):
+        """print_clusters(goldstandard=...) (Visuals.py:24-25,52-53): an example's key is its
+        first gold label, the empty label '' included (the reference's Counter drops None
+        only).  Keys are numbered by the smallest row carrying them; rows without an entry
+        get -1."""
+        rows = np.full(int(n_rows), -1, dtype=np.int32)
+        names, key_of_name = [], {}
+        for ex in sorted(e for e in (gold_split or {})
+                         if isinstance(e, (int, np.integer)) and 0 <= e < n_rows):
+            name = gold_split[ex][0]
+            k = key_of_name.get(name)
+            if k is None:
+                k = key_of_name[name] = len(names)
+                names.append(name)
+            rows[ex] = k
+        return cls(None, names, rows)
+
+
+def row_keys(X, key_of_feature, use_values=True):
+    """The host oracle of rae_row_keys: int32 per row of the CSR matrix X, the key of its first
+    stored column (CSR order) that carries one, -1 for none.  use_values: a stored 0 is not a
+    column of the row (scipy's nonzero()); False = rae_row_keys with values == NULL."""
+    kof = np.asarray(key_of_feature, dtype=np.int64)
+    indptr = np.asarray(X.indptr, dtype=np.int64)
+    idx = np.asarray(X.indices, dtype=np.int64)
+    inr = (idx >= 0) & (idx < kof.shape[0])
+    k = np.full(idx.shape[0], -1, dtype=np.int64)
+    k[inr] = kof[idx[inr]]
+    ok = k >= 0
+    if use_values:
+        ok &= np.asarray(X.data) != 0
+    pos = np.flatnonzero(ok)                                # positions that carry a key
+    j = np.searchsorted(pos, indptr[:-1], side="left")      # the first one at or after the row
+    nxt = np.append(pos, idx.shape[0])[j]                  # nnz when there is none
+    hit = nxt < indptr[1:]
+    out = np.full(indptr.shape[0] - 1, -1, dtype=np.int32)
+    out[hit] = k[nxt[hit]]
+    return out
+
+
+def key_table(labels, keys, relations, n_keys):
+    """(relations, n_keys) int32: cell (c, k) counts the rows with labels[i] == c and
+    keys[i] == k; rows with either out of range are skipped (rae_cluster_key_count)."""
+    lab = np.asarray(labels, dtype=np.int64)
+    key = np.asarray(keys, dtype=np.int64)
+    if lab.shape != key.shape:
+        raise ValueError(f"{lab.shape[0]} labels for {key.shape[0]} keys")
+    keep = (lab >= 0) & (lab < relations) & (key >= 0) & (key < n_keys)
+    cell = lab[keep] * n_keys + key[keep]
+    return np.bincount(cell, minlength=relations * n_keys).astype(np.int32).reshape(
+        relations, n_keys)
+
+
+def topk_from_table(table, top):
+    """(keys, counts), both (relations, top) int32: per row the cells with count > 0 by count
+    descending, then key ascending, cut to `top` and padded with (-1, 0) (rae_cluster_topk)."""
+    table = np.asarray(table)
+    m = table.shape[0]
+    keys = np.full((m, top), -1, dtype=np.int32)
+    counts = np.zeros((m, top), dtype=np.int32)
+    for c in range(m):
+        row = table[c].astype(np.int64)
+        nz = np.flatnonzero(row > 0)
+        order = nz[np.lexsort((nz, -row[nz]))][:top]
+        keys[c, :order.shape[0]] = order
+        counts[c, :order.shape[0]] = row[order]
+    return keys, counts
+
+
+def format_cluster_profiles(keys, counts, names):
+    """One line per cluster id 0..m-1 (empty clusters included) as print_clusters renders it:
+    `print cl_id,` then ' '.join(map(str, [(name, freq), ...])) -- the id, a space, the tuples
+    joined by spaces (an empty cluster's line is the id and the space)."""
+    lines = []
+    for c in range(len(keys)):
+        items = [(names[int(k)], int(n)) for k, n in zip(keys[c], counts[c]) if k >= 0]
+        lines.append(f"{c} " + " ".join(map(str, items)))
+    return lines

@@ -13,7 +13,8 @@ import torch
 
 from .data import SPLIT_LABELS
 from .engine import DeviceSplit, TrainEngine
-from .evaluation import GoldIndex, construct_split_evaluator
+from .evaluation import (GoldIndex, KeyIndex, construct_split_evaluator,
+                         format_cluster_profiles, key_table, row_keys, topk_from_table)
 from .model import OieModelFunctions, _as_bool, make_optimizer
 from .negatives import NegativeExampleGenerator
 
@@ -74,9 +75,21 @@ class ReconstructInducer:
                  graph_chunk=64, neg_sampler="device", neg_seed=0, mfma_bf16=False,
                  kernel_forms=None, dp_update="replicated", index_window=0,
                  index_overlap=True, p2p_cross_device=False, p2p_timeout=5.0,
-                 eval_cost=False, eval_seed=None, cluster_eval="host"):
+                 eval_cost=False, eval_seed=None, cluster_eval="host", print_clusters="off",
+                 print_top=5, print_by="trigger"):
         if cluster_eval not in ("host", "device"):
             raise ValueError("cluster_eval must be 'host' or 'device'")
+        if print_clusters not in ("off", "host", "device"):
+            raise ValueError("print_clusters must be 'off', 'host' or 'device'")
+        if print_by not in ("trigger", "gold"):
+            raise ValueError("print_by must be 'trigger' or 'gold'")
+        if print_clusters != "off":
+            if not 1 <= int(print_top) <= 32:
+                raise ValueError("print_top must be in [1, 32]")
+            if print_by == "trigger" and getattr(data, "featureLex", None) is None:
+                raise ValueError("print_clusters by trigger needs the dataset's feature lexicon "
+                                 "(a file written by rae.preprocess); this dataset has none -- "
+                                 "use print_by='gold'")
         self.data = data
         self.goldStandard = gold_standard
         self.rng = rng
@@ -125,6 +138,16 @@ class ReconstructInducer:
         # rows, same printed lines; self.cluster[split] is then not built
         self.cluster_eval = cluster_eval
         self._gold_index = {}
+        # print_clusters: after each f1 line learn() prints, per induced relation, the print_top
+        # most frequent triggers (print_by="gold": first gold labels) of its members with their
+        # frequencies (Visualizator.print_clusters, evaluation/Visuals.py:8-45) -- "host": from
+        # the downloaded labels with the numpy oracles of rae/evaluation.py; "device": the key
+        # table and top-k on the GPU (TrainEngine.cluster_profiles); the same lines either way
+        self.print_clusters = print_clusters
+        self.print_top = int(print_top)
+        self.print_by = print_by
+        self._key_index = {}
+        self._host_keys = {}
         self.negativeSampler = NegativeExampleGenerator(rng, data.negSamplingCum)   # :85
         self.modelID = (f"{decoder_model}_{model_name}_maxepoch{nb_epochs}_lr{learning_rate}"
                         f"_embedsize{embed_size}_l1{lambda1}_l2{lambda2}_opt{optimization}"
@@ -314,9 +337,10 @@ class ReconstructInducer:
             return Counter({c: int(n) for c, n in enumerate(sizes) if n})
         return Counter(int(x) for x in self._labels(split))
 
-    def _cluster_result(self, split):
+    def _cluster_result(self, split, profiles=False):
         """cluster_eval="device": TrainEngine.cluster_metrics over the rows _labels covers (the
-        first nbs * batch_size), against the split's whole gold standard."""
+        first nbs * batch_size), against the split's whole gold standard.  profiles: also the
+        cluster profiles, from the same labelling pass -> (ClusterResult, ProfileResult)."""
         if not self._check_for_compiled_functions():
             self.compile_function()
         ds = self._dev_split[split]
@@ -325,7 +349,11 @@ class ReconstructInducer:
             gi = self._gold_index[split] = GoldIndex(
                 (self.goldStandard or {}).get(split, {}), ds.N)
         nbs = self.data.split[split].args1.shape[0] // self.batch_size
-        return self.engine.cluster_metrics(ds, gi, 0, nbs * self.batch_size)
+        if profiles and self._keys_of(split).n_keys > 0:
+            return self.engine.cluster_metrics_and_profiles(
+                ds, gi, self._keys_of(split), 0, nbs * self.batch_size, self.print_top)
+        res = self.engine.cluster_metrics(ds, gi, 0, nbs * self.batch_size)
+        return (res, None) if profiles else res
 
     def _score(self, split, verbose=True):
         """learn()'s evaluation of one split: the cluster sets and the host evaluator, or
@@ -338,15 +366,58 @@ class ReconstructInducer:
         ev = self.evaluator.get(split)
         if ev is None:
             return None
+        profiles = None
         if self.cluster_eval == "device":
-            res = self._cluster_result(split)
+            if verbose and self.print_clusters == "device":    # one labelling pass for both
+                res, profiles = self._cluster_result(split, profiles=True)
+            else:
+                res = self._cluster_result(split)
             f1, pre, rec = res.f1, res.precision, res.recall
         else:
             ev.feed_induced_clusters(self.cluster[split])
             f1, pre, rec = ev.compute_metrics()
         if verbose:
             print("{} f1: {:.4f} pre: {:.4f} rec: {:.4f}".format(split, f1, pre, rec))
+            if self.print_clusters != "off":
+                for line in self.cluster_profile_lines(split, profiles):
+                    print(line)
         return f1, pre, rec
+
+    def _keys_of(self, split):
+        """The split's KeyIndex: the lexicon's triggers (one index for every split) or the
+        split's first gold labels."""
+        tag = split if self.print_by == "gold" else "*"
+        ki = self._key_index.get(tag)
+        if ki is None:
+            if self.print_by == "gold":
+                ki = KeyIndex.from_gold((self.goldStandard or {}).get(split, {}),
+                                        self.data.split[split].args1.shape[0])
+            else:
+                ki = KeyIndex.from_lexicon(self.data.featureLex)
+            self._key_index[tag] = ki
+        return ki
+
+    def cluster_profile_lines(self, split, profiles=None):
+        """print_clusters' lines for the rows _labels covers (the first nbs * batch_size): one
+        per cluster id, `print_top` (name, frequency) tuples each."""
+        ki = self._keys_of(split)
+        nrows = (self.data.split[split].args1.shape[0] // self.batch_size) * self.batch_size
+        if ki.n_keys == 0:                       # nothing to count: every cluster prints empty
+            return format_cluster_profiles([[]] * self.relationNum, [[]] * self.relationNum, [])
+        if profiles is None and self.print_clusters == "device":
+            if not self._check_for_compiled_functions():
+                self.compile_function()
+            profiles = self.engine.cluster_profiles(self._dev_split[split], ki, 0, nrows,
+                                                    self.print_top)
+        if profiles is None:
+            keys = self._host_keys.get(split)
+            if keys is None:
+                keys = ki.rows if ki.rows is not None else \
+                    row_keys(self.data.split[split].xFeats, ki.key_of_feature)
+                self._host_keys[split] = keys
+            table = key_table(self._labels(split), keys[:nrows], self.relationNum, ki.n_keys)
+            profiles = topk_from_table(table, self.print_top)
+        return format_cluster_profiles(profiles[0], profiles[1], ki.names)
 
     def _mode(self):
         """OieInduction.py:300-312."""
