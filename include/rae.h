@@ -207,6 +207,48 @@ int rae_set_negatives(rae_plan* plan, const int32_t* neg1_dev, const int32_t* ne
 int rae_build_index(rae_plan* plan, int64_t first_batch, int64_t count, rae_stream_t stream);
 int64_t rae_index_window(rae_plan* plan);
 
+/* Read-back of the row index (tests and diagnosis; read-only, outside every step path).
+ * The index dimensions the plan resolved, as RAE_INDEX_NDIMS int64 values in this order:
+ * L, l, s, G, rank, part, RA, RW, HA, HW, index_window, posbits, TC, NVC, hch, HF, dcap,
+ * dstride, dnx, priv, privnf, LA, LW  (RA / RW: record slots per batch and table; TC / NVC /
+ * HF: entries per slot of task / vtask / hfin; LA / LW: row-list capacities).  count must be
+ * RAE_INDEX_NDIMS.                                                                          */
+#define RAE_INDEX_NDIMS 23
+int rae_index_dims(const rae_plan* plan, int64_t* out, int32_t count);
+/* Regions of a batch slot (slot = batch % index_window), 32-bit ints throughout:
+ *   SREC_A / _W   RA / RW record ids, sorted by (row, record), partition after partition
+ *   SEG_A / _W    RA / RW x 4: (row, first position, end position, first record id)
+ *   COUNT_A / _W  1024 partition counts;  PCLS_A / _W  1024 x 4: (heavy, light, very heavy, offset)
+ *   THDR          4: (wave tasks, workgroup tasks, chunked rows, 0)
+ *   TASK          TC x 4;  VTASK  NVC x 4;  HFIN  HF x 4 (plans that chunk very heavy rows)
+ *   DESC          dnx x dstride;  PMASK  L x 4 (plans with private rows)
+ *   DPL           2 x G x (LA + LW) row lists, DPC 2 x G x 2 their lengths [dir][peer][table],
+ *   DPMAX         2: the longest entity / feature list since the last rae_dp_list_max (not per
+ *                 slot)  (these three: the partitioned update only)
+ * Entries behind what the counts cover are stale by design.                                 */
+#define RAE_IDXR_SREC_A 0
+#define RAE_IDXR_SREC_W 1
+#define RAE_IDXR_SEG_A 2
+#define RAE_IDXR_SEG_W 3
+#define RAE_IDXR_COUNT_A 4
+#define RAE_IDXR_COUNT_W 5
+#define RAE_IDXR_PCLS_A 6
+#define RAE_IDXR_PCLS_W 7
+#define RAE_IDXR_THDR 8
+#define RAE_IDXR_TASK 9
+#define RAE_IDXR_VTASK 10
+#define RAE_IDXR_HFIN 11
+#define RAE_IDXR_DESC 12
+#define RAE_IDXR_PMASK 13
+#define RAE_IDXR_DPL 14
+#define RAE_IDXR_DPC 15
+#define RAE_IDXR_DPMAX 16
+/* Synchronises the device, then copies the region of `batch`'s slot to host memory.  bytes
+ * must be the region's size; RAE_E_INVALID for a wrong size or a region the plan does not
+ * have (HFIN without chunks, PMASK without private rows, DPL / DPC / DPMAX outside the
+ * partitioned update).                                                                      */
+int rae_index_read(rae_plan* plan, int64_t batch, int32_t region, void* host_out, int64_t bytes);
+
 /* --- the training step (func['train']) --------------------------------------------- */
 /* Batch addressed as  batch = *cursor + step_offset  (cursor: device int64 owned by the
  * plan) so a captured sequence of steps can be replayed for successive batches.        */

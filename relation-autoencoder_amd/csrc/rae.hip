@@ -1014,6 +1014,64 @@ extern "C" int rae_build_index(rae_plan* p, int64_t first, int64_t count, rae_st
 }
 extern "C" int64_t rae_index_window(rae_plan* p) { return p ? p->args.index_window : -1; }
 
+// read-back of the row index (tests, diagnosis): outside every step path, nothing is written
+extern "C" int rae_index_dims(const rae_plan* p, int64_t* out, int32_t count) {
+    if (!p || !out) return fail(RAE_E_INVALID, "null argument");
+    if (count != RAE_INDEX_NDIMS) return fail(RAE_E_INVALID, "rae_index_dims: count must be RAE_INDEX_NDIMS");
+    const StepArgs& a = p->args;
+    const int64_t v[RAE_INDEX_NDIMS] = {
+        a.L, a.l, a.s, a.G, a.rank, a.part, a.RA, a.RW, a.HA, a.HW, a.index_window, a.posbits,
+        a.TC, a.NVC, a.hch, a.HF, a.dcap, a.dstride, a.dnx, a.priv, a.privnf, a.LA, a.LW};
+    for (int i = 0; i < RAE_INDEX_NDIMS; ++i) out[i] = v[i];
+    return RAE_OK;
+}
+extern "C" int rae_index_read(rae_plan* p, int64_t batch, int32_t region, void* host_out, int64_t bytes) {
+    if (!p || !host_out) return fail(RAE_E_INVALID, "null argument");
+    if (batch < 0) return fail(RAE_E_INVALID, "batch index out of the epoch");
+    const StepArgs& a = p->args;
+    const int64_t slot = batch % a.index_window;
+    // (base, bytes per slot) of the region; a null base: the plan has no such region
+    const char* base = nullptr;
+    int64_t per = 0;
+    auto at = [&](const void* ptr, int64_t n) { base = reinterpret_cast<const char*>(ptr); per = n; };
+    switch (region) {
+    case RAE_IDXR_SREC_A: at(a.srecA, 4ll * a.RA); break;
+    case RAE_IDXR_SREC_W: at(a.srecW, 4ll * a.RW); break;
+    case RAE_IDXR_SEG_A: at(a.urowA, 16ll * a.RA); break;
+    case RAE_IDXR_SEG_W: at(a.urowW, 16ll * a.RW); break;
+    case RAE_IDXR_COUNT_A: case RAE_IDXR_COUNT_W:      // gidx[slot][table][0]: the counts
+        at(a.gidx, 16ll * RAE_IDX_HMAX);
+        if (base) base += (region == RAE_IDXR_COUNT_W ? 8ll : 0ll) * RAE_IDX_HMAX;
+        break;
+    case RAE_IDXR_PCLS_A: case RAE_IDXR_PCLS_W:
+        at(a.pcls, 32ll * RAE_IDX_HMAX);
+        if (base) base += (region == RAE_IDXR_PCLS_W ? 16ll : 0ll) * RAE_IDX_HMAX;
+        break;
+    case RAE_IDXR_THDR: at(a.thdr, 16); break;
+    case RAE_IDXR_TASK: at(a.task, 16ll * a.TC); break;
+    case RAE_IDXR_VTASK: at(a.vtask, 16ll * a.NVC); break;
+    case RAE_IDXR_HFIN: if (a.hch) at(a.hfin, 16ll * a.HF); break;
+    case RAE_IDXR_DESC: at(a.desc, 4ll * a.dnx * a.dstride); break;
+    case RAE_IDXR_PMASK: if (a.priv) at(a.pmask, 16ll * a.L); break;
+    case RAE_IDXR_DPL: if (a.part) at(a.dpl, 4ll * dpl_slot_ints(a.G, a.LA, a.LW)); break;
+    case RAE_IDXR_DPC: if (a.part) at(a.dpc, 16ll * a.G); break;
+    case RAE_IDXR_DPMAX: if (a.part) at(a.dpmax, 0); break;
+    default: return fail(RAE_E_INVALID, "rae_index_read: unknown region");
+    }
+    if (!base) return fail(RAE_E_INVALID, "rae_index_read: the plan has no such region");
+    // what is copied: a slot of the region; the two partition tables one table's
+    // RAE_IDX_HMAX entries of the slot; dpmax its two words (not per slot)
+    int64_t want = per;
+    if (region == RAE_IDXR_COUNT_A || region == RAE_IDXR_COUNT_W) want = 4ll * RAE_IDX_HMAX;
+    if (region == RAE_IDXR_PCLS_A || region == RAE_IDXR_PCLS_W) want = 16ll * RAE_IDX_HMAX;
+    if (region == RAE_IDXR_DPMAX) want = 8;
+    if (bytes != want)
+        return fail(RAE_E_INVALID, "rae_index_read: the region holds " + std::to_string(want) + " bytes");
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(host_out, base + slot * per, (size_t)want, hipMemcpyDeviceToHost));
+    return RAE_OK;
+}
+
 extern "C" int rae_step_forward(rae_plan* p, int64_t off, rae_stream_t stream) {
     if (!p) return fail(RAE_E_INVALID, "null plan");
     return launch_forward(p, p->d_cursor, off, (hipStream_t)stream);

@@ -208,7 +208,9 @@ __device__ void index_count(const StepArgs& a, int64_t g, int64_t slot, int tab,
     int* hist = sh;
     int* sptr = sh + RAE_IDX_HMAX;
     if (t.H > RAE_IDX_HMAX || t.nrec > t.Rcap) {
-        if (tid == 0) atomicOr(a.err, tab ? 2 : 1);
+        // more records than the plan's slots hold (max_batch_nnz understated): error bit 4;
+        // nothing of this table is built for the batch
+        if (tid == 0) atomicOr(a.err, t.nrec > t.Rcap ? 4 : (tab ? 2 : 1));
         return;
     }
     for (int h = tid; h < t.H; h += BT) hist[h] = 0;
@@ -526,8 +528,11 @@ __device__ void build_batch_tasks(const StepArgs& a, int64_t g, int64_t slot, in
     const int4* clsT[2] = {idx_cls(a, slot, 0), idx_cls(a, slot, 1)};
     int tot[2][3];
     for (int tab = 0; tab < 2; ++tab) {
-        Ht[tab] = idx_tab(a, g, slot, tab).H;
-        if (Ht[tab] > RAE_IDX_HMAX) Ht[tab] = 0;           // flagged by k_idx_count
+        const IdxTab it = idx_tab(a, g, slot, tab);
+        Ht[tab] = it.H;
+        // flagged by k_idx_count: no partition of the table was sorted, and pcls holds whatever
+        // the slot's previous batch left there -- the table contributes no task
+        if (Ht[tab] > RAE_IDX_HMAX || it.nrec > it.Rcap) Ht[tab] = 0;
         for (int c = 0; c < 3; ++c) {
             int* pf = sh + (tab * 3 + c) * (RAE_IDX_HMAX + 1);
             int x = 0;

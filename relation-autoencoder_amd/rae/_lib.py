@@ -71,6 +71,7 @@ EXPORTS = (
     "rae_set_cursor", "rae_advance_cursor", "rae_cursor_moves", "rae_step_forward",
     "rae_step_update", "rae_step_forward_at", "rae_step_update_at",
     "rae_train_step", "rae_check", "rae_check_on", "rae_label", "rae_build_index", "rae_index_window",
+    "rae_index_dims", "rae_index_read",
     "rae_neg_sample", "rae_neg_sample_philox",
     "rae_time_next", "rae_event_create", "rae_event_destroy", "rae_event_elapsed_ms",
     "rae_stream_copy", "rae_mfma_probe", "rae_plan_forms",
@@ -83,6 +84,14 @@ EXPORTS = (
     "rae_row_keys", "rae_cluster_key_count", "rae_cluster_topk",
 )
 RAE_IPC_HANDLE_BYTES = 64
+# rae_index_dims' values in order, and rae_index_read's regions (include/rae.h RAE_IDXR_*)
+INDEX_DIMS = ("L", "l", "s", "G", "rank", "part", "RA", "RW", "HA", "HW", "index_window",
+              "posbits", "TC", "NVC", "hch", "HF", "dcap", "dstride", "dnx", "priv", "privnf",
+              "LA", "LW")
+INDEX_REGIONS = {name: code for code, name in enumerate(
+    ("srecA", "srecW", "segA", "segW", "countA", "countW", "pclsA", "pclsW", "thdr", "task",
+     "vtask", "hfin", "desc", "pmask", "dpl", "dpc", "dpmax"))}
+RAE_IDX_HMAX = 1024               # partition table entries per batch slot and table
 # rae_cluster_count forms (include/rae.h RAE_CCOUNT_*)
 RAE_CCOUNT_AUTO = 0
 RAE_CCOUNT_LDS = 1
@@ -221,6 +230,10 @@ def load(path: str | None = None):
     lib.rae_build_index.argtypes = [_P, C.c_int64, C.c_int64, _P]
     lib.rae_index_window.argtypes = [_P]
     lib.rae_index_window.restype = C.c_int64
+    lib.rae_index_dims.argtypes = [_P, C.POINTER(C.c_int64), C.c_int32]
+    lib.rae_index_dims.restype = C.c_int
+    lib.rae_index_read.argtypes = [_P, C.c_int64, C.c_int32, _P, C.c_int64]
+    lib.rae_index_read.restype = C.c_int
     lib.rae_label.argtypes = [_P, _P, _P, _P, _P, C.c_int32, C.c_int64, C.c_int64, _P, _P, _P]
     lib.rae_eval_workspace_bytes.argtypes = [C.POINTER(RaeEvalArgs)]
     lib.rae_eval_workspace_bytes.restype = C.c_int64

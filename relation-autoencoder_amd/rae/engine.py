@@ -632,6 +632,29 @@ class TrainEngine:
         if self._dp:
             self._dp_caps_check()
 
+    def index_dims(self):
+        """The row index's dimensions as the plan resolved them (rae_index_dims)."""
+        v = (C.c_int64 * len(_lib.INDEX_DIMS))()
+        _lib.check(self.lib.rae_index_dims(self.plan, v, len(_lib.INDEX_DIMS)), "rae_index_dims")
+        return dict(zip(_lib.INDEX_DIMS, (int(x) for x in v)))
+
+    def index_region(self, batch: int, region: str):
+        """One region of `batch`'s index slot as a host int32 array (rae_index_read; waits for
+        the device).  A read-back for tests and diagnosis: no step path calls it."""
+        d = self.index_dims()
+        H = _lib.RAE_IDX_HMAX
+        shape = {"srecA": (d["RA"],), "srecW": (d["RW"],), "segA": (d["RA"], 4),
+                 "segW": (d["RW"], 4), "countA": (H,), "countW": (H,), "pclsA": (H, 4),
+                 "pclsW": (H, 4), "thdr": (4,), "task": (d["TC"], 4), "vtask": (d["NVC"], 4),
+                 "hfin": (d["HF"], 4), "desc": (d["dnx"], d["dstride"]), "pmask": (d["L"], 4),
+                 "dpl": (2, d["G"], d["LA"] + d["LW"]), "dpc": (2, d["G"], 2),
+                 "dpmax": (2,)}[region]
+        out = np.empty(shape, dtype=np.int32)
+        _lib.check(self.lib.rae_index_read(self.plan, int(batch), _lib.INDEX_REGIONS[region],
+                                           out.ctypes.data_as(C.c_void_p), out.nbytes),
+                   "rae_index_read")
+        return out
+
     def run(self, first_batch: int, count: int, graph: bool = True, index: bool = True,
             last_advance: bool = True, prefetch: bool | None = None, sync_peers: bool = True):
         """Run ``count`` consecutive global batches starting at ``first_batch`` on the epoch
