@@ -406,6 +406,68 @@ typedef struct rae_eval_args {
 int64_t rae_eval_workspace_bytes(const rae_eval_args* a);
 int rae_eval_cost(const rae_eval_args* a, rae_stream_t stream);
 
+/* --- argument ranking over the whole entity vocabulary (no reference counterpart: the reference
+ * only scores s sampled negatives) ------------------------------------------------------------ */
+/* rae_rank_queries: nq queries against all n_entities rows of A.  The score of entity e for query
+ * q is  g_q(e) = <Q[q, :embed], A[e]> + (add[q] + Ab[e])  (add / Ab NULL: zero), one k-ascending
+ * fp32 fmaf chain on v_mfma_f32_32x32x2_f32 (no split-K), never written to memory.  Outputs, over
+ * the entities e in [0, n_entities) other than skip[q] (skip NULL or outside [0, n): nothing is
+ * skipped):
+ *     greater[q] = #{e : g_q(e) > target[q]}      equal[q] = #{e : g_q(e) == target[q]}
+ *     lse[q] = log sum_e exp g_q(e)  (-inf when nothing is summed; lse may be NULL)
+ * A query's three outputs are bitwise independent of nq, of its position and of the other
+ * queries; the log-sum-exp is folded per entity strip (a count fixed by n_entities alone, at most
+ * 128) and the strips are merged in order.  Every pointer is a device pointer except the struct.
+ * Plan-free, stream-ordered, capturable: allocates nothing, never synchronises, writes only
+ * greater, equal, lse and workspace; arguments are checked before the first HIP call.
+ * Limits: nq >= 0 (0 is valid), 1 <= n_entities < 2^31, 1 <= embed <= 1024, ldq >= embed,
+ * ldq % 4 == 0, Q 16-byte aligned, A 16-byte aligned when embed % 4 == 0, workspace 256-byte
+ * aligned.  With nq == 0 no pointer is read.  Long query lists run in chunks of 4096.         */
+typedef struct rae_rank_args {
+    const float *Q; int64_t ldq; int64_t nq;
+    const float *add;           /* (nq), may be NULL                                           */
+    const float *target;        /* (nq)                                                        */
+    const int32_t *skip;        /* (nq), may be NULL                                           */
+    const float *A, *Ab;        /* (n_entities, embed), (n_entities) or NULL                   */
+    int64_t n_entities; int32_t embed;
+    int32_t *greater, *equal;   /* (nq)                                                        */
+    float *lse;                 /* (nq), may be NULL                                           */
+    void *workspace; int64_t workspace_bytes;
+} rae_rank_args;
+int rae_rank_queries(const rae_rank_args* a, rae_stream_t stream);
+
+/* rae_eval_rank: both arguments of rows [row0, row0+nrows) of a split ranked against all
+ * entities at the current parameters, with rae_eval_cost's scores.  P = softmax(x W + Wb),
+ * a1 = A[args1], a2 = A[args2], M = sum_k P_k R3[:,:,k]:
+ *     decoder     q1 (replaces arg 1)   q2 (replaces arg 2)   c1          c2          one
+ *     sp          C1 P                  C2 P                  <C2 P,a1>   <C1 P,a1>   c1 + c2
+ *     rescal      M a2                  M^T a1                0           0           <a1,q1>
+ *     rescal+sp   M a2 + C1 P           M^T a1 + C2 P         <C2 P,a2>   <C1 P,a1>   <a1,q1> + c1
+ * Query 2b + t - 1 (row b, side t): candidates g_t(e) = <A[e], q_t> + (c_t + Ab[e]), target
+ * u_t = one + Ab[args_t] (the objective's positive score; SP keeps the reference's A[args1]-twice
+ * behaviour, so u_2 != g_2(args2)), the true entity args_t left out.  Outputs as
+ * rae_rank_queries', (nrows, 2).  Derived in double: rank = 1 + greater + equal / 2,
+ * logp = u - logaddexp(u, lse);  summary[8 side + j], side = t - 1:
+ *     j = 0 sum 1/rank   1 sum rank   2 sum logp   3..6 #{rank <= hits_k[j - 3]}   7 nrows
+ * summed like rae_eval_cost's sums (one partial per 1024 rows, added in row order).
+ * Reads decoder, shapes, parameters, CSR, args1 / args2, row0 / nrows and the workspace of `a`;
+ * neg_samples, neg1, neg2, neg_stride, terms_out and sums_out are not read.  Shape limits are
+ * rae_eval_cost's; rows run in chunks of 2048.  Plan-free, stream-ordered, capturable; writes
+ * only the outputs and the workspace; per-query outputs are bitwise independent of row0, nrows
+ * and the other rows.  nrows == 0 is valid (a zero summary).                                    */
+typedef struct rae_rank_out {
+    int32_t *greater, *equal;   /* (nrows, 2); not read when nrows == 0                        */
+    float *target, *lse;        /* (nrows, 2), each may be NULL                                */
+    double *summary;            /* 16 doubles, may be NULL                                     */
+    int32_t hits_k[4];          /* <= 0: unused                                                */
+} rae_rank_out;
+int rae_eval_rank(const rae_eval_args* a, const rae_rank_out* out, rae_stream_t stream);
+
+/* bytes of workspace of rae_rank_queries (q, with e NULL) or of rae_eval_rank (e, with q NULL);
+ * host only, no HIP call; -1 on a bad argument or unless exactly one is given.  Reads the shapes
+ * only; independent of nq / nrows; depends on n_entities only through the strip count (<= 128). */
+int64_t rae_rank_workspace_bytes(const rae_rank_args* q, const rae_eval_args* e);
+
 /* --- cluster evaluation (get_clusters_sets learning/OieInduction.py:321-340;
  *     evaluation/OieEvaluation.py:23-44,90-127) ------------------------------------ */
 /* Plan-free and stream-ordered like rae_label / rae_eval_cost: every pointer is a device

@@ -34,6 +34,7 @@
 #include "rae_label.hpp"
 #include "rae_p2p.hpp"
 #include "rae_profile.hpp"
+#include "rae_rank.hpp"
 #include "rae_sampler.hpp"
 #include "rae_sp.hpp"
 #include "rae_step.hpp"
@@ -550,6 +551,51 @@ __global__ void k_eval_acc(const double* partial, int nblk, double* sums, int in
     double t = init ? 0.0 : sums[c];
     for (int b = 0; b < nblk; ++b) t += partial[b * 3 + c];
     sums[c] = t;
+}
+
+// ---- argument ranking over all entities (rae_rank.hpp) ----
+template <bool V4>
+__global__ __launch_bounds__(RAE_EV_BT) void k_rank_build(EvalArgs a, RankBuild o) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    rank_build<V4>(a, o, reinterpret_cast<float*>(smem));
+}
+__global__ void k_rank_zero(int32_t* greater, int32_t* equal, int nq) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q < nq) { greater[q] = 0; equal[q] = 0; }
+}
+template <bool AV4, bool LSE>
+__global__ __launch_bounds__(RAE_RK_BT) void k_rank(RankArgs a) {
+    __shared__ float sQ[RAE_RK_TQ * RAE_RK_LDK];
+    __shared__ float sA[RAE_RK_TE * RAE_RK_LDK];
+    __shared__ float sAb[RAE_RK_TE];
+    __shared__ float2 sPart[RAE_RK_TQ];
+    rank_scores<AV4, LSE>(a, sQ, sA, sAb, sPart);
+}
+// lse[q] of the chunk: the strips' (max, sum) pairs merged in strip order
+__global__ void k_rank_finish(const float2* part, int strips, int nq, float* lse) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nq) return;
+    float m = -INFINITY, s = 0.f;
+    for (int t = 0; t < strips; ++t) {
+        const float2 o = part[(int64_t)t * RAE_RK_QCHUNK + q];
+        rank_lse_merge(m, s, o.x, o.y);
+    }
+    lse[q] = m == -INFINITY ? -INFINITY : m + logf(s);
+}
+__global__ __launch_bounds__(RAE_EV_BT) void k_rank_blocksum(const int32_t* greater,
+                                                             const int32_t* equal,
+                                                             const float* target, const float* lse,
+                                                             int n, RankHits hk, double* partial) {
+    __shared__ double red[RAE_EV_NW * RAE_RK_NSUM];
+    rank_blocksum(greater, equal, target, lse, n, hk, partial, red);
+}
+// summary[c] (+)= the chunk's partials in block order (init: the first chunk sets)
+__global__ void k_rank_acc(const double* partial, int nblk, double* summary, int init) {
+    const int c = threadIdx.x;
+    if (blockIdx.x != 0 || c >= RAE_RK_NSUM) return;
+    double t = init ? 0.0 : summary[c];
+    for (int b = 0; b < nblk; ++b) t += partial[b * RAE_RK_NSUM + c];
+    summary[c] = t;
 }
 
 __global__ void k_add_cursor(int64_t* cursor, int64_t count) {
@@ -1398,7 +1444,8 @@ struct EvalLayout {
 };
 inline size_t ev_align(size_t x) { return (x + 255) & ~(size_t)255; }
 // argument check (host only) and the workspace layout
-int eval_check(const rae_eval_args* a, EvalLayout& L, bool need_buffers) {
+// the shape limits of the evaluation kernels (rae_eval_cost, rae_eval_rank)
+int eval_shapes(const rae_eval_args* a, bool need_s) {
     if (!a) return fail(RAE_E_INVALID, "null argument");
     if (a->decoder < 0 || a->decoder > 2) return fail(RAE_E_INVALID, "decoder must be 0..2");
     const int m = a->relations, r = a->embed, s = a->neg_samples;
@@ -1406,12 +1453,18 @@ int eval_check(const rae_eval_args* a, EvalLayout& L, bool need_buffers) {
     if ((m % 4) != 0 && m > 128)
         return fail(RAE_E_INVALID, "relations must be a multiple of 4 above 128");
     if (r < 1 || r > 1024) return fail(RAE_E_INVALID, "embed must be in [1, 1024]");
-    if (s < 1) return fail(RAE_E_INVALID, "neg_samples must be >= 1");
+    if (need_s && s < 1) return fail(RAE_E_INVALID, "neg_samples must be >= 1");
     const bool bil = a->decoder != RAE_DEC_SP;
     if (bil && eval_mt_lds_bytes(m) > 160 * 1024)
         return fail(RAE_E_INVALID, "relations must be <= 320 for the bilinear decoders");
     if (eval_dec_lds_floats(a->decoder, m, r) * 4 > 160 * 1024)
         return fail(RAE_E_INVALID, "relations / embed need more than 160 KiB of LDS per tile");
+    return RAE_OK;
+}
+int eval_check(const rae_eval_args* a, EvalLayout& L, bool need_buffers) {
+    if (const int rc = eval_shapes(a, true)) return rc;
+    const int m = a->relations, r = a->embed;
+    const bool bil = a->decoder != RAE_DEC_SP;
     L.chunk = bil ? RAE_EV_CHUNK_BIL : RAE_EV_CHUNK_SP;
     const size_t ch = (size_t)L.chunk, r4 = (size_t)eval_r4(r);
     size_t o = 0;
@@ -1514,6 +1567,214 @@ extern "C" int rae_eval_cost(const rae_eval_args* a, rae_stream_t stream) {
                            (const float*)e.terms, n, partial);
         hipLaunchKernelGGL(k_eval_acc, dim3(1), dim3(64), 0, st, (const double*)partial, nblk,
                            a->sums_out, c0 == 0 ? 1 : 0);
+        HIPCHK(hipGetLastError());
+    }
+    return RAE_OK;
+}
+
+// ---- argument ranking over all entities -------------------------------------------------------
+namespace {
+struct RankLayout {                          // rae_eval_rank's workspace
+    size_t o_partial, o_terms, o_P, o_v, o_w, o_Q, o_c, o_u, o_skip, o_lse, o_part, total;
+};
+inline size_t rank_part_bytes(int64_t n) {
+    return ev_align((size_t)rank_strips(n) * RAE_RK_QCHUNK * sizeof(float2));
+}
+// shapes of rae_rank_queries (host only)
+int rank_shapes(const rae_rank_args* a) {
+    if (!a) return fail(RAE_E_INVALID, "null argument");
+    if (a->embed < 1 || a->embed > 1024) return fail(RAE_E_INVALID, "embed must be in [1, 1024]");
+    if (a->n_entities < 1 || a->n_entities >= (1ll << 31))
+        return fail(RAE_E_INVALID, "n_entities must be in [1, 2^31)");
+    return RAE_OK;
+}
+// shapes of rae_eval_rank and its workspace layout (host only)
+int eval_rank_layout(const rae_eval_args* a, RankLayout& L) {
+    if (const int rc = eval_shapes(a, false)) return rc;
+    if (a->n_entities < 1 || a->n_entities >= (1ll << 31))
+        return fail(RAE_E_INVALID, "n_entities must be in [1, 2^31)");
+    const int m = a->relations, r = a->embed;
+    const bool bil = a->decoder != RAE_DEC_SP;
+    const size_t ch = RAE_RK_ROWCHUNK, r4 = (size_t)eval_r4(r);
+    size_t o = 0;
+    L.o_partial = o; o = ev_align(o + (ch / RAE_EV_SUMROWS) * RAE_RK_NSUM * sizeof(double));
+    L.o_terms = o;   o = ev_align(o + ch * 3 * sizeof(float));
+    L.o_P = o;       if (bil) o = ev_align(o + ch * m * sizeof(float));
+    L.o_v = o;       if (bil) o = ev_align(o + (size_t)eval_nbj(r) * ch * r4 * sizeof(float));
+    L.o_w = o;       if (bil) o = ev_align(o + (size_t)eval_nbi(r) * ch * r4 * sizeof(float));
+    L.o_Q = o;       o = ev_align(o + 2 * ch * r4 * sizeof(float));
+    L.o_c = o;       o = ev_align(o + 2 * ch * sizeof(float));
+    L.o_u = o;       o = ev_align(o + 2 * ch * sizeof(float));
+    L.o_skip = o;    o = ev_align(o + 2 * ch * sizeof(int32_t));
+    L.o_lse = o;     o = ev_align(o + 2 * ch * sizeof(float));
+    L.o_part = o;    o += rank_part_bytes(a->n_entities);
+    L.total = o;
+    return RAE_OK;
+}
+// one chunk (k.nq <= RAE_RK_QCHUNK queries) on the stream: zero, scores, the lse's finish
+void rank_launch(RankArgs k, float* lse, hipStream_t st) {
+    const int strips = rank_strips(k.n);
+    k.tps = rank_tiles_per_strip(k.n);
+    k.ntiles = rank_tiles(k.n);
+    const bool av4 = (k.r % 4) == 0;
+    hipLaunchKernelGGL(k_rank_zero, dim3((unsigned)ceil_div(k.nq, 256)), dim3(256), 0, st,
+                       k.greater, k.equal, k.nq);
+    const dim3 grid((unsigned)ceil_div(k.nq, RAE_RK_TQ), (unsigned)strips);
+    with_bool(av4, [&](auto V) {
+        with_bool(lse != nullptr, [&](auto L) {
+            hipLaunchKernelGGL((k_rank<RAE_CV(V), RAE_CV(L)>), grid, dim3(RAE_RK_BT), 0, st, k);
+        });
+    });
+    if (lse)
+        hipLaunchKernelGGL(k_rank_finish, dim3((unsigned)ceil_div(k.nq, 256)), dim3(256), 0, st,
+                           (const float2*)k.part, strips, k.nq, lse);
+}
+}  // namespace
+
+extern "C" int64_t rae_rank_workspace_bytes(const rae_rank_args* q, const rae_eval_args* e) {
+    if ((q != nullptr) == (e != nullptr))
+        return fail(RAE_E_INVALID, "give exactly one of the two argument structs"), -1;
+    if (q) {
+        if (rank_shapes(q)) return -1;
+        return (int64_t)rank_part_bytes(q->n_entities);
+    }
+    RankLayout L;
+    if (eval_rank_layout(e, L)) return -1;
+    return (int64_t)L.total;
+}
+
+extern "C" int rae_rank_queries(const rae_rank_args* a, rae_stream_t stream) {
+    if (const int rc = rank_shapes(a)) return rc;
+    if (a->nq < 0) return fail(RAE_E_INVALID, "nq must be >= 0");
+    if (a->ldq < a->embed) return fail(RAE_E_INVALID, "ldq is smaller than embed");
+    if (a->ldq % 4) return fail(RAE_E_INVALID, "ldq must be a multiple of 4");
+    if (a->nq == 0) return RAE_OK;            // nothing is read or written
+    if (!a->Q) return fail(RAE_E_INVALID, "Q is NULL");
+    if ((uintptr_t)a->Q & 15) return fail(RAE_E_INVALID, "Q must be 16-byte aligned");
+    if (!a->target) return fail(RAE_E_INVALID, "target is NULL");
+    if (!a->A) return fail(RAE_E_INVALID, "A is NULL");
+    if ((a->embed % 4) == 0 && ((uintptr_t)a->A & 15))
+        return fail(RAE_E_INVALID, "A must be 16-byte aligned");
+    if (!a->greater || !a->equal) return fail(RAE_E_INVALID, "greater / equal is NULL");
+    if (!a->workspace) return fail(RAE_E_INVALID, "workspace is NULL");
+    if ((uintptr_t)a->workspace & 255) return fail(RAE_E_INVALID, "workspace must be 256-byte aligned");
+    if (a->workspace_bytes < (int64_t)rank_part_bytes(a->n_entities))
+        return fail(RAE_E_INVALID, "workspace_bytes is smaller than rae_rank_workspace_bytes()");
+    hipStream_t st = (hipStream_t)stream;
+    for (int64_t c0 = 0; c0 < a->nq; c0 += RAE_RK_QCHUNK) {
+        RankArgs k;
+        k.Q = a->Q + c0 * a->ldq; k.ldq = a->ldq;
+        k.add = a->add ? a->add + c0 : nullptr;
+        k.target = a->target + c0;
+        k.skip = a->skip ? a->skip + c0 : nullptr;
+        k.A = a->A; k.Ab = a->Ab; k.n = a->n_entities; k.r = a->embed;
+        k.nq = (int)std::min<int64_t>(RAE_RK_QCHUNK, a->nq - c0);
+        k.greater = a->greater + c0; k.equal = a->equal + c0;
+        k.part = (float2*)a->workspace;
+        rank_launch(k, a->lse ? a->lse + c0 : nullptr, st);
+        HIPCHK(hipGetLastError());
+    }
+    return RAE_OK;
+}
+
+extern "C" int rae_eval_rank(const rae_eval_args* a, const rae_rank_out* out, rae_stream_t stream) {
+    RankLayout L;
+    if (const int rc = eval_rank_layout(a, L)) return rc;
+    if (!out) return fail(RAE_E_INVALID, "out is NULL");
+    if (a->nrows < 0) return fail(RAE_E_INVALID, "nrows must be >= 0");
+    if (a->row0 < 0 || a->row0 + a->nrows >= (1ll << 31))
+        return fail(RAE_E_INVALID, "row0 / nrows out of range");
+    const int m = a->relations, r = a->embed;
+    const bool bil = a->decoder != RAE_DEC_SP, v4 = (m % 4) == 0;
+    if (!a->W) return fail(RAE_E_INVALID, "W is NULL");
+    if (!a->Wb) return fail(RAE_E_INVALID, "Wb is NULL");
+    if (!a->A) return fail(RAE_E_INVALID, "A is NULL");
+    if (!a->Ab) return fail(RAE_E_INVALID, "Ab is NULL");
+    if (a->decoder != RAE_DEC_RESCAL && (!a->C1 || !a->C2))
+        return fail(RAE_E_INVALID, "C1 / C2 is NULL");
+    if (bil && !a->R3) return fail(RAE_E_INVALID, "R3 is NULL");
+    if (!a->indptr || !a->indices) return fail(RAE_E_INVALID, "indptr / indices is NULL");
+    if (!a->args1 || !a->args2) return fail(RAE_E_INVALID, "args1 / args2 is NULL");
+    if (a->nrows > 0 && (!out->greater || !out->equal))
+        return fail(RAE_E_INVALID, "greater / equal is NULL");
+    if (!a->workspace) return fail(RAE_E_INVALID, "workspace is NULL");
+    if ((uintptr_t)a->workspace & 255) return fail(RAE_E_INVALID, "workspace must be 256-byte aligned");
+    if (a->workspace_bytes < (int64_t)L.total)
+        return fail(RAE_E_INVALID, "workspace_bytes is smaller than rae_rank_workspace_bytes()");
+    if (v4 && (((uintptr_t)a->W | (uintptr_t)a->Wb | (uintptr_t)a->C1 | (uintptr_t)a->C2 |
+                (uintptr_t)a->R3) & 15))
+        return fail(RAE_E_INVALID, "W / Wb / C1 / C2 / R3 must be 16-byte aligned");
+    if ((r % 4) == 0 && ((uintptr_t)a->A & 15))
+        return fail(RAE_E_INVALID, "A must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)a->workspace;
+    double* partial = (double*)(ws + L.o_partial);
+    const size_t lds_dec = eval_dec_lds_floats(a->decoder, m, r) * 4;
+    const size_t lds_mt = eval_mt_lds_bytes(m);
+    if (lds_dec > 48 * 1024) {
+        HIPCHK(hipFuncSetAttribute(v4 ? (const void*)k_rank_build<true> : (const void*)k_rank_build<false>,
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_dec));
+    }
+    if (bil && lds_mt > 48 * 1024) {
+        HIPCHK(hipFuncSetAttribute(v4 ? (const void*)k_eval_mt<true> : (const void*)k_eval_mt<false>,
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_mt));
+    }
+    EvalArgs e;
+    e.dec = a->decoder; e.m = m; e.r = r; e.s = 0; e.alpha = a->alpha;
+    e.W = a->W; e.Wb = a->Wb; e.A = a->A; e.Ab = a->Ab; e.C1 = a->C1; e.C2 = a->C2; e.R3 = a->R3;
+    e.indptr = a->indptr; e.indices = a->indices; e.values = a->values;
+    e.args1 = a->args1; e.args2 = a->args2; e.neg1 = nullptr; e.neg2 = nullptr;
+    e.neg_stride = 0;
+    e.cap = RAE_RK_ROWCHUNK; e.r4 = eval_r4(r);
+    e.terms = (float*)(ws + L.o_terms);
+    e.P = (float*)(ws + L.o_P); e.vpart = (float*)(ws + L.o_v); e.wpart = (float*)(ws + L.o_w);
+    const bool want_lse = out->lse || out->summary;
+    RankHits hk;
+    for (int j = 0; j < 4; ++j) hk.k[j] = out->hits_k[j];
+    if (a->nrows == 0) {
+        if (out->summary) {
+            hipLaunchKernelGGL(k_rank_acc, dim3(1), dim3(64), 0, st, (const double*)partial, 0,
+                               out->summary, 1);
+            HIPCHK(hipGetLastError());
+        }
+        return RAE_OK;
+    }
+    for (int64_t c0 = 0; c0 < a->nrows; c0 += RAE_RK_ROWCHUNK) {
+        const int n = (int)std::min<int64_t>(RAE_RK_ROWCHUNK, a->nrows - c0);
+        e.row0 = a->row0 + c0;
+        e.n = n;
+        if (bil) {
+            const dim3 ge((unsigned)std::min(ceil_div(n, RAE_EV_NW), 65536));
+            const dim3 gm((unsigned)(eval_nbi(r) * eval_nbj(r)));
+            with_bool(v4, [&](auto V) {
+                hipLaunchKernelGGL(k_eval_enc<RAE_CV(V)>, ge, dim3(RAE_EV_BT), 0, st, e);
+                hipLaunchKernelGGL(k_eval_mt<RAE_CV(V)>, gm, dim3(RAE_EV_MTT), lds_mt, st, e);
+            });
+        }
+        RankBuild b;
+        b.Q = (float*)(ws + L.o_Q);
+        b.c = (float*)(ws + L.o_c);
+        b.u = out->target ? out->target + 2 * c0 : (float*)(ws + L.o_u);
+        b.skip = (int32_t*)(ws + L.o_skip);
+        const dim3 gd((unsigned)ceil_div(n, RAE_EV_TE));
+        with_bool(v4, [&](auto V) {
+            hipLaunchKernelGGL(k_rank_build<RAE_CV(V)>, gd, dim3(RAE_EV_BT), lds_dec, st, e, b);
+        });
+        RankArgs k;
+        k.Q = b.Q; k.ldq = e.r4; k.add = b.c; k.target = b.u; k.skip = b.skip;
+        k.A = a->A; k.Ab = a->Ab; k.n = a->n_entities; k.r = r; k.nq = 2 * n;
+        k.greater = out->greater + 2 * c0; k.equal = out->equal + 2 * c0;
+        k.part = (float2*)(ws + L.o_part);
+        float* lse = !want_lse ? nullptr : (out->lse ? out->lse + 2 * c0 : (float*)(ws + L.o_lse));
+        rank_launch(k, lse, st);
+        if (out->summary) {
+            const int nblk = ceil_div(n, RAE_EV_SUMROWS);
+            hipLaunchKernelGGL(k_rank_blocksum, dim3((unsigned)nblk), dim3(RAE_EV_BT), 0, st,
+                               (const int32_t*)k.greater, (const int32_t*)k.equal,
+                               (const float*)b.u, (const float*)lse, n, hk, partial);
+            hipLaunchKernelGGL(k_rank_acc, dim3(1), dim3(64), 0, st, (const double*)partial, nblk,
+                               out->summary, c0 == 0 ? 1 : 0);
+        }
         HIPCHK(hipGetLastError());
     }
     return RAE_OK;

@@ -370,18 +370,35 @@ __device__ __forceinline__ void eval_mt(const EvalArgs& a, float* smem) {
     }
 }
 
-// ---- k_eval_dec: the tile's scores ------------------------------------------------------------
+// ---- the tile's contraction vectors and positive scores (shared with rae_rank.hpp) ------------
+// LDS of one tile of RAE_EV_TE examples (eval_dec_lds_floats)
+struct EvalTile {
+    float* sP;                                // the tile's P
+    float* sL;                                // contracted with the neg1 rows (and a1)
+    float* sR;                                // contracted with the neg2 rows
+    float* sC1;                               // hybrid: wC1, wC2
+    float* sC2;
+};
+__device__ __forceinline__ EvalTile eval_tile(const EvalArgs& a, float* sm) {
+    const int mS = (a.m + 3) & ~3, r4 = a.r4;
+    EvalTile t;
+    t.sP = sm;
+    t.sL = t.sP + RAE_EV_TE * mS;
+    t.sR = t.sL + RAE_EV_TE * r4;
+    t.sC1 = t.sR + RAE_EV_TE * r4;
+    t.sC2 = t.sC1 + RAE_EV_TE * r4;
+    return t;
+}
+
+// phases 1 - 2b of a tile: sL / sR (hybrid: sC1 / sC2 too) of the workgroup's RAE_EV_TE examples;
+// ends on a barrier
 template <bool V4>
-__device__ __forceinline__ void eval_dec(const EvalArgs& a, float* sm) {
-    const int m = a.m, r = a.r, s = a.s, dec = a.dec;
+__device__ __forceinline__ void eval_tile_vectors(const EvalArgs& a, const EvalTile& T) {
+    const int m = a.m, r = a.r, dec = a.dec;
     const int mS = (m + 3) & ~3, r4 = a.r4;
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    float* sP = sm;
-    float* sL = sP + RAE_EV_TE * mS;          // contracted with the neg1 rows (and a1)
-    float* sR = sL + RAE_EV_TE * r4;          // contracted with the neg2 rows
-    float* sC1 = sR + RAE_EV_TE * r4;         // hybrid: wC1, wC2
-    float* sC2 = sC1 + RAE_EV_TE * r4;
+    float *sP = T.sP, *sL = T.sL, *sR = T.sR, *sC1 = T.sC1, *sC2 = T.sC2;
     const int tb = blockIdx.x * RAE_EV_TE;
     // ---- phase 1: the tile's P in LDS (SP: the encoder here; hybrid: from the workspace)
     if (dec != 1) {
@@ -431,6 +448,42 @@ __device__ __forceinline__ void eval_dec(const EvalArgs& a, float* sm) {
         }
         __syncthreads();
     }
+}
+
+// the positive dots of example slot q of the tile by one wave: one (the objective's positive
+// score without the entity bias), addL (added to every neg1 score) and addR (to every neg2 score)
+__device__ __forceinline__ void eval_positive(const EvalArgs& a, const EvalTile& T, int q, int e1,
+                                              int e2, float& one, float& addL, float& addR) {
+    const int r = a.r, r4 = a.r4, dec = a.dec;
+    const int lane = threadIdx.x & 63;
+    const int grp = lane >> 4, sub = lane & 15;
+    const float *sC1 = T.sC1, *sC2 = T.sC2;
+    const float* vL = T.sL + q * r4;
+    const float* vR = T.sR + q * r4;
+    // positives.  SP (A[args1] twice, the reference's behaviour): left = <wC1,a1>,
+    // right = <wC2,a1>.  RESCAL: one = <a1, M a2>.  Hybrid: <a1, M a2 + wC1>, sp2 =
+    // <wC2,a2>, sp1 = <wC1,a1>
+    const int prow = (dec == 2 && grp == 1) ? e2 : e1;
+    const float* pvec = dec == 0 ? (grp == 1 ? vR : vL)
+                                 : (dec == 1 ? vL
+                                             : (grp == 0 ? vL : (grp == 1 ? sC2 + q * r4
+                                                                          : sC1 + q * r4)));
+    const float pd = eval_dot(a.A + (int64_t)prow * r, pvec, r, sub);
+    const float d0 = __shfl(pd, 0, 64), d1 = __shfl(pd, 16, 64), d2 = __shfl(pd, 32, 64);
+    if (dec == 0) { one = d0 + d1; addL = d1; addR = d0; }
+    else if (dec == 1) { one = d0; addL = 0.f; addR = 0.f; }
+    else { one = d0 + d1; addL = d1; addR = d2; }
+}
+
+// ---- k_eval_dec: the tile's scores ------------------------------------------------------------
+template <bool V4>
+__device__ __forceinline__ void eval_dec(const EvalArgs& a, float* sm) {
+    const int r = a.r, s = a.s, r4 = a.r4;
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int tb = blockIdx.x * RAE_EV_TE;
+    const EvalTile T = eval_tile(a, sm);
+    eval_tile_vectors<V4>(a, T);
     // ---- phase 3: per example (one wave each) the A-row gathers, four rows per instruction
     const int grp = lane >> 4, sub = lane & 15;
     for (int q = w; q < RAE_EV_TE; q += RAE_EV_NW) {
@@ -438,22 +491,10 @@ __device__ __forceinline__ void eval_dec(const EvalArgs& a, float* sm) {
         if (b >= a.n) continue;
         const int64_t ex = a.row0 + b;
         const int e1 = a.args1[ex], e2 = a.args2[ex];
-        const float* vL = sL + q * r4;
-        const float* vR = sR + q * r4;
-        // positives.  SP (A[args1] twice, the reference's behaviour): left = <wC1,a1>,
-        // right = <wC2,a1>.  RESCAL: one = <a1, M a2>.  Hybrid: <a1, M a2 + wC1>, sp2 =
-        // <wC2,a2>, sp1 = <wC1,a1>
-        const int prow = (dec == 2 && grp == 1) ? e2 : e1;
-        const float* pvec = dec == 0 ? (grp == 1 ? vR : vL)
-                                     : (dec == 1 ? vL
-                                                 : (grp == 0 ? vL : (grp == 1 ? sC2 + q * r4
-                                                                              : sC1 + q * r4)));
-        const float pd = eval_dot(a.A + (int64_t)prow * r, pvec, r, sub);
-        const float d0 = __shfl(pd, 0, 64), d1 = __shfl(pd, 16, 64), d2 = __shfl(pd, 32, 64);
-        float one, addL, addR;        // addL: added to every neg1 score, addR: to every neg2 score
-        if (dec == 0) { one = d0 + d1; addL = d1; addR = d0; }
-        else if (dec == 1) { one = d0; addL = 0.f; addR = 0.f; }
-        else { one = d0 + d1; addL = d1; addR = d2; }
+        const float* vL = T.sL + q * r4;
+        const float* vR = T.sR + q * r4;
+        float one, addL, addR;
+        eval_positive(a, T, q, e1, e2, one, addL, addR);
         const float pos = eval_logsig(one + a.Ab[e1]) + eval_logsig(one + a.Ab[e2]);
         // negatives: task t < s: neg1[t] against vL; s <= t < 2s: neg2[t - s] against vR
         float nacc = 0.f;

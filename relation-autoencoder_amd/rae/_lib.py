@@ -80,6 +80,7 @@ EXPORTS = (
     "rae_ipc_export", "rae_ipc_open", "rae_ipc_close", "rae_p2p_signals", "rae_set_peer",
     "rae_set_p2p_timeout", "rae_p2p_prologue",
     "rae_eval_workspace_bytes", "rae_eval_cost",
+    "rae_rank_queries", "rae_eval_rank", "rae_rank_workspace_bytes",
     "rae_cluster_count", "rae_b3_metrics",
     "rae_row_keys", "rae_cluster_key_count", "rae_cluster_topk",
 )
@@ -162,6 +163,28 @@ class RaeEvalArgs(C.Structure):
     ]
 
 
+class RaeRankArgs(C.Structure):
+    """rae_rank_args (include/rae.h): caller-given queries against every entity."""
+    _fields_ = [
+        ("Q", _P), ("ldq", C.c_int64), ("nq", C.c_int64), ("add", _P), ("target", _P),
+        ("skip", _P), ("A", _P), ("Ab", _P), ("n_entities", C.c_int64), ("embed", C.c_int32),
+        ("greater", _P), ("equal", _P), ("lse", _P),
+        ("workspace", _P), ("workspace_bytes", C.c_int64),
+    ]
+
+
+class RaeRankOut(C.Structure):
+    """rae_rank_out (include/rae.h): the outputs of rae_eval_rank."""
+    _fields_ = [
+        ("greater", _P), ("equal", _P), ("target", _P), ("lse", _P), ("summary", _P),
+        ("hits_k", C.c_int32 * 4),
+    ]
+
+
+# the rank kernel's tile and strip constants (csrc/rae_rank.hpp RAE_RK_*)
+RAE_RK_TQ, RAE_RK_TE, RAE_RK_MAXSTRIPS, RAE_RK_QCHUNK, RAE_RK_ROWCHUNK = 128, 128, 128, 4096, 2048
+
+
 class RaeError(RuntimeError):
     pass
 
@@ -239,6 +262,12 @@ def load(path: str | None = None):
     lib.rae_eval_workspace_bytes.restype = C.c_int64
     lib.rae_eval_cost.argtypes = [C.POINTER(RaeEvalArgs), _P]
     lib.rae_eval_cost.restype = C.c_int
+    lib.rae_rank_queries.argtypes = [C.POINTER(RaeRankArgs), _P]
+    lib.rae_rank_queries.restype = C.c_int
+    lib.rae_eval_rank.argtypes = [C.POINTER(RaeEvalArgs), C.POINTER(RaeRankOut), _P]
+    lib.rae_eval_rank.restype = C.c_int
+    lib.rae_rank_workspace_bytes.argtypes = [C.POINTER(RaeRankArgs), C.POINTER(RaeEvalArgs)]
+    lib.rae_rank_workspace_bytes.restype = C.c_int64
     lib.rae_cluster_count.argtypes = [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P]
     lib.rae_cluster_count.restype = C.c_int
     lib.rae_b3_metrics.argtypes = [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P]

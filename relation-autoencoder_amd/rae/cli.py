@@ -71,6 +71,13 @@ def get_command_args(argv=None, program_name="rae"):
                         "evaluated splits (train, or valid and test)")
     p.add_argument("--eval-seed", dest="eval_seed", type=int, default=None,
                    help="key of the fixed negatives the objective is scored against")
+    p.add_argument("--eval-rank", dest="eval_rank", action="store_true", default=False,
+                   help="after each epoch also rank the true arguments of the evaluated splits "
+                        "among all entities (MRR, mean rank, hits@k, exact log-likelihood)")
+    p.add_argument("--eval-rank-ks", dest="eval_rank_ks", type=_int_list, default=(1, 10, 100),
+                   help="comma-separated hits@k thresholds of --eval-rank (at most four)")
+    p.add_argument("--eval-rank-rows", dest="eval_rank_rows", type=int, default=None,
+                   help="rank only the first N rows of each split (default: the whole split)")
     p.add_argument("--cluster-eval", dest="cluster_eval", choices=["host", "device"],
                    default="host",
                    help="where the induced clusters are scored: the host evaluator, or the "
@@ -108,6 +115,16 @@ def get_command_args(argv=None, program_name="rae"):
     return a
 
 
+def _int_list(text):
+    try:
+        ks = tuple(int(x) for x in text.split(",") if x.strip())
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not a comma-separated list of integers: {text!r}")
+    if not 1 <= len(ks) <= 4 or any(k < 1 for k in ks):
+        raise argparse.ArgumentTypeError("one to four thresholds, each >= 1")
+    return ks
+
+
 def load_dataset(spec: str, seed: int = 1234):
     from .data import load_npz, synthetic_dataset
     if spec.startswith("synthetic:"):
@@ -143,7 +160,8 @@ def main(argv=None):
                              eval_cost=args.eval_cost, eval_seed=args.eval_seed,
                              cluster_eval=args.cluster_eval,
                              print_clusters=args.print_clusters, print_top=args.print_top,
-                             print_by=args.print_by)
+                             print_by=args.print_by, eval_rank=args.eval_rank,
+                             eval_rank_ks=args.eval_rank_ks, eval_rank_rows=args.eval_rank_rows)
     if exchange is not None:
         ind.compile_function()
         rdist.warm_up(exchange, ind.engine.exchange_buf)

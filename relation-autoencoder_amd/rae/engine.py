@@ -32,6 +32,9 @@ _hip = None
 # TrainEngine.evaluate's result: cost = reconstruction + entropy (Python floats), the
 # (nrows, 3) terms tensor (or None) and the three double column sums (S_pos, S_H, S_neg)
 EvalResult = collections.namedtuple("EvalResult", "cost reconstruction entropy terms sums")
+# TrainEngine.rank: mrr / mean_rank / logp are (side 1, side 2, combined), hits {k: such a tuple}
+RankResult = collections.namedtuple(
+    "RankResult", "mrr mean_rank hits logp nrows summary greater equal target lse")
 # TrainEngine.cluster_metrics' result: B^3 f1 / precision / recall (Python floats), the number
 # of clustered elements (int), the cluster sizes (numpy int64, relations) and the
 # (relations, n_gold + 1) contingency table (numpy int64, or None when not asked for)
@@ -101,7 +104,7 @@ class TrainEngine:
         self.model = model
         self.device = device if device is not None else model.params[0].device
         self.world_size = int(world_size)
-        self.rank = int(rank)
+        self.dp_rank = int(rank)     # data-parallel rank (rank() is the argument ranking)
         self.exchange = exchange
         self.graph_chunk = int(graph_chunk)
         dec = model.decoder
@@ -127,7 +130,7 @@ class TrainEngine:
         cfg.neg_samples = self.s
         cfg.batch_size = self.l
         cfg.world_size = self.world_size
-        cfg.rank = self.rank
+        cfg.rank = self.dp_rank
         cfg.learning_rate = float(learning_rate)
         cfg.alpha = float(model.alpha)
         cfg.lambda1 = float(lambda1)
@@ -293,7 +296,7 @@ class TrainEngine:
         _lib.check(self.lib.rae_set_p2p_timeout(self.plan, C.c_double(self._p2p_timeout)),
                    "rae_set_p2p_timeout")
         for p, e in enumerate(everyone):
-            if p == self.rank:
+            if p == self.dp_rank:
                 continue
             ptr = {k: self._ipc_map(*e[k]) for k in ("ex", "W", "A", "Ab", "sig")}
             _lib.check(self.lib.rae_set_peer(self.plan, p, C.c_void_p(ptr["ex"]),
@@ -940,6 +943,79 @@ class TrainEngine:
         a.sums_out = p(self._eval_sums)
         a.workspace, a.workspace_bytes = p(self._eval_ws), int(self._eval_ws.numel())
         _lib.check(self.lib.rae_eval_cost(C.byref(a), self._stream()), "rae_eval_cost")
+
+    # ------------------------------------------------------------------ argument ranking
+    def rank(self, split: DeviceSplit, row0: int = 0, nrows: int | None = None,
+             ks=(1, 10, 100), per_query: bool = False):
+        """Where the true argument ranks among ALL entities, and its exact softmax
+        log-likelihood, for rows [row0, row0+nrows) of `split` at the current parameters
+        (rae_eval_rank; the scores are rae_eval_cost's).  RankResult: mrr, mean_rank, hits
+        ({k: fraction}), logp (mean log-likelihood), each a (side 1, side 2, combined) tuple;
+        per_query=True: also the (nrows, 2) tensors greater, equal, target, lse.  Reads back 16
+        doubles once.  Touches no parameter, accumulator, plan state, cursor, negative or RNG.
+        Partitioned update with stale rows: gathers the parameters first (a collective, like
+        evaluate; every rank ranks the whole range)."""
+        if self.stale(accumulators=False):
+            self.sync_replicas(accumulators=False)
+        row0 = int(row0)
+        nrows = split.N - row0 if nrows is None else int(nrows)
+        if row0 < 0 or nrows < 0 or row0 + nrows > split.N:
+            raise IndexError(f"rows [{row0}, {row0 + nrows}) out of the split's {split.N}")
+        ks = tuple(int(k) for k in ks)
+        if len(ks) > 4 or any(k < 1 for k in ks):
+            raise ValueError("ks: at most four thresholds, each >= 1")
+        out = self.queue_rank(split, row0, nrows, ks, per_query)
+        s = self._rank_summary.cpu().numpy()
+        n = float(nrows)
+
+        def three(j, scale=1.0):
+            a, b = float(s[j]), float(s[8 + j])
+            if nrows == 0:
+                return (0.0, 0.0, 0.0)
+            return (a / n * scale, b / n * scale, (a + b) / (2.0 * n) * scale)
+        hits = {k: three(3 + j) for j, k in enumerate(ks)}
+        return RankResult(three(0), three(1), hits, three(2), nrows, tuple(float(x) for x in s),
+                          *(out if per_query else (None, None, None, None)))
+
+    def queue_rank(self, split: DeviceSplit, row0: int, nrows: int, ks=(1, 10, 100),
+                   per_query: bool = False, out=None):
+        """Queue rae_eval_rank on the current stream (no host synchronisation): the summary
+        into self._rank_summary (16 doubles), the per-query outputs into `out` = (greater, equal,
+        target, lse), (nrows, 2) each (allocated here unless given; target / lse only with
+        per_query).  Returns `out`.  rank() is this plus the read-back;
+        tools/rank_eval_bench.py times it alone."""
+        named = self._named
+        R3 = named.get("R", named.get("C"))
+        a = _lib.RaeEvalArgs()
+        a.decoder = self.cfg.decoder
+        a.relations, a.embed = self.m, self.r
+        a.n_entities = self.cfg.n_entities
+        a.alpha = self.cfg.alpha
+        p = _lib.ptr
+        a.W, a.Wb, a.A, a.Ab = p(named["W"]), p(named["Wb"]), p(named["A"]), p(named["Ab"])
+        a.C1, a.C2, a.R3 = p(named.get("C1")), p(named.get("C2")), p(R3)
+        a.indptr, a.indices, a.values = p(split.indptr), p(split.indices), p(split.values)
+        a.args1, a.args2 = p(split.args1), p(split.args2)
+        a.row0, a.nrows = int(row0), int(nrows)
+        if getattr(self, "_rank_ws", None) is None:      # once per engine
+            need = int(self.lib.rae_rank_workspace_bytes(None, C.byref(a)))
+            if need < 0:
+                _lib.check(-1, "rae_rank_workspace_bytes")
+            self._rank_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+            self._rank_summary = torch.zeros(16, dtype=torch.float64, device=self.device)
+        if out is None:
+            mk = lambda dt: torch.empty((nrows, 2), dtype=dt, device=self.device)
+            out = (mk(torch.int32), mk(torch.int32),
+                   mk(torch.float32) if per_query else None,
+                   mk(torch.float32) if per_query else None)
+        a.workspace, a.workspace_bytes = p(self._rank_ws), int(self._rank_ws.numel())
+        o = _lib.RaeRankOut()
+        o.greater, o.equal, o.target, o.lse = p(out[0]), p(out[1]), p(out[2]), p(out[3])
+        o.summary = p(self._rank_summary)
+        for j in range(4):
+            o.hits_k[j] = int(ks[j]) if j < len(ks) else 0
+        _lib.check(self.lib.rae_eval_rank(C.byref(a), C.byref(o), self._stream()), "rae_eval_rank")
+        return out
 
     # ------------------------------------------------------------------ cluster evaluation
     def _gold_dev(self, split: DeviceSplit, gold_index):

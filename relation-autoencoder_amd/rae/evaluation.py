@@ -159,6 +159,37 @@ def b3_from_table(table, sizes, n_assessable):
 
 
 # ---------------------------------------------------------------------------------------------
+# argument ranking over all entities (rae_eval_rank): the numpy oracle of its summary kernel
+# ---------------------------------------------------------------------------------------------
+def rank_summary(greater, equal, target, lse, ks=(1, 10, 100)):
+    """The 16 doubles rae_eval_rank's summary kernel writes, from its per-query outputs (each
+    (nrows, 2): column t - 1 = the side whose argument is replaced).  In float64:
+        rank = 1 + greater + equal / 2        logp = target - logaddexp(target, lse)
+    out[8 side + j]: j = 0 sum 1/rank, 1 sum rank, 2 sum logp, 3..6 the number of rows with
+    rank <= ks[j - 3] (up to four ks; a k <= 0 or a missing one counts nothing), 7 nrows."""
+    ks = list(ks)
+    if len(ks) > 4:
+        raise ValueError("at most four hit thresholds")
+    g = np.asarray(greater, dtype=np.float64).reshape(-1, 2)
+    e = np.asarray(equal, dtype=np.float64).reshape(-1, 2)
+    u = np.asarray(target, dtype=np.float64).reshape(-1, 2)
+    l = np.asarray(lse, dtype=np.float64).reshape(-1, 2)
+    rank = 1.0 + g + 0.5 * e
+    with np.errstate(invalid="ignore"):
+        logp = np.where(np.isneginf(l), 0.0, u - np.logaddexp(u, l))
+    out = np.zeros(16, np.float64)
+    for side in range(2):
+        out[8 * side + 0] = (1.0 / rank[:, side]).sum()
+        out[8 * side + 1] = rank[:, side].sum()
+        out[8 * side + 2] = logp[:, side].sum()
+        for j, k in enumerate(ks):
+            if k > 0:
+                out[8 * side + 3 + j] = float((rank[:, side] <= k).sum())
+        out[8 * side + 7] = float(rank.shape[0])
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
 # per-cluster profiles (Visualizator.print_clusters, evaluation/Visuals.py:8-45): for every
 # induced relation the most frequent triggers (or gold labels) of its members
 # ---------------------------------------------------------------------------------------------

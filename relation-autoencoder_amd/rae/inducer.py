@@ -76,7 +76,8 @@ class ReconstructInducer:
                  kernel_forms=None, dp_update="replicated", index_window=0,
                  index_overlap=True, p2p_cross_device=False, p2p_timeout=5.0,
                  eval_cost=False, eval_seed=None, cluster_eval="host", print_clusters="off",
-                 print_top=5, print_by="trigger"):
+                 print_top=5, print_by="trigger", eval_rank=False, eval_rank_ks=(1, 10, 100),
+                 eval_rank_rows=None):
         if cluster_eval not in ("host", "device"):
             raise ValueError("cluster_eval must be 'host' or 'device'")
         if print_clusters not in ("off", "host", "device"):
@@ -132,6 +133,15 @@ class ReconstructInducer:
         self.eval_cost = bool(eval_cost)
         self.eval_seed = eval_seed
         self.eval_costs = {s: [] for s in SPLIT_LABELS}
+        # eval_rank: learn() also ranks the true arguments of the splits it evaluates among all
+        # entities after each epoch (TrainEngine.rank: MRR, mean rank, hits@k, mean exact
+        # log-likelihood); eval_rank_rows: the first N rows only (default: the whole split)
+        self.eval_rank = bool(eval_rank)
+        self.eval_rank_ks = tuple(int(k) for k in eval_rank_ks)
+        if len(self.eval_rank_ks) > 4 or any(k < 1 for k in self.eval_rank_ks):
+            raise ValueError("eval_rank_ks: at most four thresholds, each >= 1")
+        self.eval_rank_rows = None if eval_rank_rows is None else int(eval_rank_rows)
+        self.rank_metrics = {s: [] for s in SPLIT_LABELS}
         # cluster_eval: where learn() scores the induced clusters -- "host": the label download
         # and the Python sets of the reference (get_clusters_sets + SingleLabelClusterEvaluation);
         # "device": the contingency table and B^3 on the GPU (TrainEngine.cluster_metrics), same
@@ -186,6 +196,7 @@ class ReconstructInducer:
         self.train_errors = []
         self.epoch_costs = []
         self.eval_costs = {s: [] for s in SPLIT_LABELS}
+        self.rank_metrics = {s: [] for s in SPLIT_LABELS}
         self.modelFunc = OieModelFunctions(self.rng, self.embedSize, self.relationNum,
                                            self.neg_sample_num, self.batch_size,
                                            self.decoder_type, self.data, self.extendedReg,
@@ -304,6 +315,9 @@ class ReconstructInducer:
             if self.eval_cost:
                 for split in (SPLIT_LABELS[:1] if self._mode() == 1 else SPLIT_LABELS[1:]):
                     self.evaluate_cost(split, verbose=verbose)
+            if self.eval_rank:
+                for split in (SPLIT_LABELS[:1] if self._mode() == 1 else SPLIT_LABELS[1:]):
+                    self.evaluate_rank(split, verbose=verbose)
         return self.train_errors
 
     def evaluate_cost(self, split, verbose=True):
@@ -316,6 +330,23 @@ class ReconstructInducer:
         if verbose:
             print("{} objective: {:.6f} (reconstruction {:.6f}, entropy {:.6f})".format(
                 split, res.cost, res.reconstruction, res.entropy))
+        return res
+
+    def evaluate_rank(self, split, verbose=True):
+        """The true arguments of `split` (its first eval_rank_rows rows) ranked among all
+        entities at the current parameters; the RankResult is appended to rank_metrics[split]."""
+        if not self._check_for_compiled_functions():
+            self.compile_function()
+        ds = self._dev_split[split]
+        nrows = ds.N if self.eval_rank_rows is None else max(0, min(ds.N, self.eval_rank_rows))
+        res = self.engine.rank(ds, 0, nrows, ks=self.eval_rank_ks)
+        self.rank_metrics[split].append(res)
+        if verbose:
+            hits = " ".join("hits@{} {:.4f}".format(k, v[2]) for k, v in res.hits.items())
+            print("{} ranking: MRR {:.6f} (arg1 {:.6f}, arg2 {:.6f}) mean rank {:.1f} {} "
+                  "log-likelihood {:.6f} ({} rows)".format(
+                      split, res.mrr[2], res.mrr[0], res.mrr[1], res.mean_rank[2], hits,
+                      res.logp[2], res.nrows))
         return res
 
     # ------------------------------------------------------------------ clusters / eval

@@ -71,12 +71,12 @@ def loopback_p2p_setup(eng):
     eng._loop = []
     sig = int(eng.lib.rae_p2p_signals(eng.plan))
     for p in range(eng.world_size):
-        if p != eng.rank:
+        if p != eng.dp_rank:
             bufs = [torch.zeros_like(eng.exchange_buf), torch.empty_like(named["W"]),
                     torch.empty_like(named["A"]), torch.empty_like(named["Ab"])]
             eng._loop.append(bufs)
             ex, W, A, Ab = (C.c_void_p(t.data_ptr()) for t in bufs)
-            rc = eng.lib.rae_set_peer(eng.plan, p, ex, W, A, Ab, C.c_void_p(sig + 4 * (p - eng.rank)))
+            rc = eng.lib.rae_set_peer(eng.plan, p, ex, W, A, Ab, C.c_void_p(sig + 4 * (p - eng.dp_rank)))
             assert rc == 0, eng.lib.rae_last_error()
 
 
