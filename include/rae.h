@@ -468,6 +468,64 @@ int rae_eval_rank(const rae_eval_args* a, const rae_rank_out* out, rae_stream_t 
  * only; independent of nq / nrows; depends on n_entities only through the strip count (<= 128). */
 int64_t rae_rank_workspace_bytes(const rae_rank_args* q, const rae_eval_args* e);
 
+/* --- top-k entity retrieval: argument prediction and the selectional preferences of an induced
+ * relation (no reference counterpart) ---------------------------------------------------------- */
+/* rae_topk_queries: the `top` best-scoring entities of each of nq queries, with their scores.
+ * The score g_q(e) is exactly rae_rank_queries': acc + (add[q] + Ab[e]) with acc the one
+ * k-ascending fp32 fmaf chain on v_mfma_f32_32x32x2_f32 (no split-K; this entry runs a
+ * copy of the rank kernel's K loop, to be kept identical to it), so both give the same bits for the same (Q row, A row, embed, add, Ab).
+ * Candidates of query q: the entities e in [0, n_entities) other than skip[q] (skip NULL or outside
+ * [0, n): nothing is skipped) whose score is not NaN.  -0.0f counts and is returned as +0.0f, so
+ * the order on scores is the order of float comparison.  Row q of the outputs is its candidates
+ * ordered by score descending, then entity ascending (a total order: the output is unique), cut
+ * to `top` entries and padded with (-1, -inf); top > n_entities is valid.
+ * A query's row is bitwise independent of nq, of its position and of the other queries.  Every
+ * pointer is a device pointer except the struct.  Plan-free, stream-ordered, capturable:
+ * allocates nothing, never synchronises, writes only ents_out, scores_out and workspace;
+ * arguments are checked before the first HIP call.
+ * Limits: rae_rank_queries' (nq >= 0, 0 is valid and reads no pointer; 1 <= n_entities < 2^31,
+ * 1 <= embed <= 1024, ldq >= embed, ldq % 4 == 0, Q 16-byte aligned, A 16-byte aligned when
+ * embed % 4 == 0, workspace 256-byte aligned) and 1 <= top <= 32.  Long query lists run in
+ * rounds of 1024.                                                                               */
+typedef struct rae_topk_args {
+    const float *Q; int64_t ldq; int64_t nq;
+    const float *add;           /* (nq) or NULL                                                */
+    const int32_t *skip;        /* (nq) or NULL: entity left out of query q                    */
+    const float *A, *Ab;        /* (n_entities, embed), (n_entities) or NULL                   */
+    int64_t n_entities; int32_t embed;
+    int32_t top;                /* 1..32                                                       */
+    int32_t *ents_out;          /* (nq, top)                                                   */
+    float   *scores_out;        /* (nq, top), may be NULL                                      */
+    void *workspace; int64_t workspace_bytes;
+} rae_topk_args;
+int rae_topk_queries(const rae_topk_args* a, rae_stream_t stream);
+
+/* rae_eval_topk: the `top` best entities for both arguments of rows [row0, row0+nrows) of a split
+ * at the current parameters.  Queries and constants are rae_eval_rank's (the table above, query
+ * 2b + t - 1 of row b); ents / scores are (nrows, 2, top) with rae_topk_queries' order and padding.
+ * skip_true != 0 leaves the row's true entity args_t out of side t, as rae_eval_rank does;
+ * skip_true == 0 ranks every entity.  Note for 'sp': side 2's score of args2 is then
+ * g_2(args2) = <A[args2], C2 P> + c_2 + Ab[args2], not the objective's positive score u_2 (the
+ * reference's A[args1]-twice behaviour, see rae_eval_rank).
+ * Reads the fields of `a` that rae_eval_rank reads, with the same shape limits; rows run in rounds
+ * of 2048.  Plan-free, stream-ordered, capturable; writes only the outputs and the workspace; a
+ * row's outputs are bitwise independent of row0, nrows and the other rows.  nrows == 0 is valid
+ * and writes nothing.                                                                           */
+typedef struct rae_topk_out {
+    int32_t *ents;              /* (nrows, 2, top); not read when nrows == 0                   */
+    float   *scores;            /* (nrows, 2, top), may be NULL                                */
+    int32_t top;                /* 1..32                                                       */
+    int32_t skip_true;          /* != 0: the row's true entity args_t is left out              */
+} rae_topk_out;
+int rae_eval_topk(const rae_eval_args* a, const rae_topk_out* out, rae_stream_t stream);
+
+/* bytes of workspace of rae_topk_queries (q, with e NULL) or of rae_eval_topk (e, with q NULL) at
+ * `top`; host only, no HIP call; -1 on a bad argument or unless exactly one is given.  Reads the
+ * shapes only; independent of nq / nrows; depends on n_entities only through the strip count
+ * (<= 128).  The strips' lists of one round of 1024 queries, 8 bytes a key: at most 32 MiB at
+ * top = 32; rae_eval_topk adds rae_eval_rank's query buffers of one round of rows.             */
+int64_t rae_topk_workspace_bytes(const rae_topk_args* q, const rae_eval_args* e, int32_t top);
+
 /* --- cluster evaluation (get_clusters_sets learning/OieInduction.py:321-340;
  *     evaluation/OieEvaluation.py:23-44,90-127) ------------------------------------ */
 /* Plan-free and stream-ordered like rae_label / rae_eval_cost: every pointer is a device

@@ -35,6 +35,7 @@
 #include "rae_p2p.hpp"
 #include "rae_profile.hpp"
 #include "rae_rank.hpp"
+#include "rae_topk.hpp"
 #include "rae_sampler.hpp"
 #include "rae_sp.hpp"
 #include "rae_step.hpp"
@@ -596,6 +597,19 @@ __global__ void k_rank_acc(const double* partial, int nblk, double* summary, int
     double t = init ? 0.0 : summary[c];
     for (int b = 0; b < nblk; ++b) t += partial[b * RAE_RK_NSUM + c];
     summary[c] = t;
+}
+
+// ---- top-k entity retrieval (rae_topk.hpp) ----
+template <bool AV4>
+__global__ __launch_bounds__(RAE_RK_BT) void k_topk(RankArgs a, TopkOut o) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    topk_scores<AV4>(a, o, smem);
+}
+__global__ __launch_bounds__(RAE_ETK_FQ * 64) void k_topk_finish(const rae_key64* keys, int strips,
+                                                                  int nq, int top, int32_t* ents,
+                                                                  float* scores) {
+    __shared__ rae_key64 sList[RAE_ETK_FQ * 32];
+    topk_finish(keys, strips, nq, top, ents, scores, sList);
 }
 
 __global__ void k_add_cursor(int64_t* cursor, int64_t count) {
@@ -1776,6 +1790,200 @@ extern "C" int rae_eval_rank(const rae_eval_args* a, const rae_rank_out* out, ra
                                out->summary, c0 == 0 ? 1 : 0);
         }
         HIPCHK(hipGetLastError());
+    }
+    return RAE_OK;
+}
+
+// ---- top-k entity retrieval ---------------------------------------------------------------------
+namespace {
+struct TopkLayout {                          // rae_eval_topk's workspace
+    size_t o_terms, o_P, o_v, o_w, o_Q, o_c, o_u, o_skip, o_keys, total;
+};
+// the strips' kept lists of one round of RAE_ETK_QCHUNK queries
+inline size_t topk_keys_bytes(int64_t n, int top) {
+    return ev_align((size_t)rank_strips(n) * RAE_ETK_QCHUNK * (size_t)top * sizeof(rae_key64));
+}
+int topk_top(int32_t top) {
+    if (top < 1 || top > RAE_ETK_MAXTOP) return fail(RAE_E_INVALID, "top must be in [1, 32]");
+    return RAE_OK;
+}
+// shapes of rae_topk_queries (host only)
+int topk_shapes(const rae_topk_args* a) {
+    if (!a) return fail(RAE_E_INVALID, "null argument");
+    if (a->embed < 1 || a->embed > 1024) return fail(RAE_E_INVALID, "embed must be in [1, 1024]");
+    if (a->n_entities < 1 || a->n_entities >= (1ll << 31))
+        return fail(RAE_E_INVALID, "n_entities must be in [1, 2^31)");
+    return RAE_OK;
+}
+// shapes of rae_eval_topk and its workspace layout (host only)
+int eval_topk_layout(const rae_eval_args* a, int32_t top, TopkLayout& L) {
+    if (const int rc = eval_shapes(a, false)) return rc;
+    if (a->n_entities < 1 || a->n_entities >= (1ll << 31))
+        return fail(RAE_E_INVALID, "n_entities must be in [1, 2^31)");
+    if (const int rc = topk_top(top)) return rc;
+    const int m = a->relations, r = a->embed;
+    const bool bil = a->decoder != RAE_DEC_SP;
+    const size_t ch = RAE_RK_ROWCHUNK, r4 = (size_t)eval_r4(r);
+    size_t o = 0;
+    L.o_terms = o;   o = ev_align(o + ch * 3 * sizeof(float));
+    L.o_P = o;       if (bil) o = ev_align(o + ch * m * sizeof(float));
+    L.o_v = o;       if (bil) o = ev_align(o + (size_t)eval_nbj(r) * ch * r4 * sizeof(float));
+    L.o_w = o;       if (bil) o = ev_align(o + (size_t)eval_nbi(r) * ch * r4 * sizeof(float));
+    L.o_Q = o;       o = ev_align(o + 2 * ch * r4 * sizeof(float));
+    L.o_c = o;       o = ev_align(o + 2 * ch * sizeof(float));
+    L.o_u = o;       o = ev_align(o + 2 * ch * sizeof(float));
+    L.o_skip = o;    o = ev_align(o + 2 * ch * sizeof(int32_t));
+    L.o_keys = o;    o += topk_keys_bytes(a->n_entities, top);
+    L.total = o;
+    return RAE_OK;
+}
+// k.nq queries on the stream in rounds of RAE_ETK_QCHUNK: selection per strip, then the merge
+int topk_launch(RankArgs k, int64_t nq, int top, rae_key64* keys, int32_t* ents, float* scores,
+                hipStream_t st) {
+    const int strips = rank_strips(k.n);
+    k.tps = rank_tiles_per_strip(k.n);
+    k.ntiles = rank_tiles(k.n);
+    k.target = nullptr; k.greater = nullptr; k.equal = nullptr; k.part = nullptr;
+    const bool av4 = (k.r % 4) == 0;
+    // large dynamic LDS is opted into per kernel (not a stream operation)
+    HIPCHK(hipFuncSetAttribute(av4 ? (const void*)k_topk<true> : (const void*)k_topk<false>,
+                               hipFuncAttributeMaxDynamicSharedMemorySize, RAE_ETK_LDS_BYTES));
+    const RankArgs base = k;
+    for (int64_t c0 = 0; c0 < nq; c0 += RAE_ETK_QCHUNK) {
+        k.Q = base.Q + c0 * base.ldq;
+        k.add = base.add ? base.add + c0 : nullptr;
+        k.skip = base.skip ? base.skip + c0 : nullptr;
+        k.nq = (int)std::min<int64_t>(RAE_ETK_QCHUNK, nq - c0);
+        TopkOut o;
+        o.keys = keys; o.top = top;
+        const dim3 grid((unsigned)ceil_div(k.nq, RAE_RK_TQ), (unsigned)strips);
+        with_bool(av4, [&](auto V) {
+            hipLaunchKernelGGL(k_topk<RAE_CV(V)>, grid, dim3(RAE_RK_BT), RAE_ETK_LDS_BYTES, st, k, o);
+        });
+        hipLaunchKernelGGL(k_topk_finish, dim3((unsigned)ceil_div(k.nq, RAE_ETK_FQ)),
+                           dim3(RAE_ETK_FQ * 64), 0, st, (const rae_key64*)keys, strips, k.nq, top,
+                           ents + c0 * top, scores ? scores + c0 * top : nullptr);
+        HIPCHK(hipGetLastError());
+    }
+    return RAE_OK;
+}
+}  // namespace
+
+extern "C" int64_t rae_topk_workspace_bytes(const rae_topk_args* q, const rae_eval_args* e,
+                                            int32_t top) {
+    if ((q != nullptr) == (e != nullptr))
+        return fail(RAE_E_INVALID, "give exactly one of the two argument structs"), -1;
+    if (q) {
+        if (topk_shapes(q) || topk_top(top)) return -1;
+        return (int64_t)topk_keys_bytes(q->n_entities, top);
+    }
+    TopkLayout L;
+    if (eval_topk_layout(e, top, L)) return -1;
+    return (int64_t)L.total;
+}
+
+extern "C" int rae_topk_queries(const rae_topk_args* a, rae_stream_t stream) {
+    if (const int rc = topk_shapes(a)) return rc;
+    if (const int rc = topk_top(a->top)) return rc;
+    if (a->nq < 0) return fail(RAE_E_INVALID, "nq must be >= 0");
+    if (a->ldq < a->embed) return fail(RAE_E_INVALID, "ldq is smaller than embed");
+    if (a->ldq % 4) return fail(RAE_E_INVALID, "ldq must be a multiple of 4");
+    if (a->nq == 0) return RAE_OK;            // nothing is read or written
+    if (!a->Q) return fail(RAE_E_INVALID, "Q is NULL");
+    if ((uintptr_t)a->Q & 15) return fail(RAE_E_INVALID, "Q must be 16-byte aligned");
+    if (!a->A) return fail(RAE_E_INVALID, "A is NULL");
+    if ((a->embed % 4) == 0 && ((uintptr_t)a->A & 15))
+        return fail(RAE_E_INVALID, "A must be 16-byte aligned");
+    if (!a->ents_out) return fail(RAE_E_INVALID, "ents_out is NULL");
+    if (!a->workspace) return fail(RAE_E_INVALID, "workspace is NULL");
+    if ((uintptr_t)a->workspace & 255) return fail(RAE_E_INVALID, "workspace must be 256-byte aligned");
+    if (a->workspace_bytes < (int64_t)topk_keys_bytes(a->n_entities, a->top))
+        return fail(RAE_E_INVALID, "workspace_bytes is smaller than rae_topk_workspace_bytes()");
+    RankArgs k;
+    k.Q = a->Q; k.ldq = a->ldq; k.add = a->add; k.skip = a->skip;
+    k.A = a->A; k.Ab = a->Ab; k.n = a->n_entities; k.r = a->embed; k.nq = 0;
+    return topk_launch(k, a->nq, a->top, (rae_key64*)a->workspace, a->ents_out, a->scores_out,
+                       (hipStream_t)stream);
+}
+
+extern "C" int rae_eval_topk(const rae_eval_args* a, const rae_topk_out* out, rae_stream_t stream) {
+    if (!out) return fail(RAE_E_INVALID, "out is NULL");
+    TopkLayout L;
+    if (const int rc = eval_topk_layout(a, out->top, L)) return rc;
+    if (a->nrows < 0) return fail(RAE_E_INVALID, "nrows must be >= 0");
+    if (a->row0 < 0 || a->row0 + a->nrows >= (1ll << 31))
+        return fail(RAE_E_INVALID, "row0 / nrows out of range");
+    const int m = a->relations, r = a->embed, top = out->top;
+    const bool bil = a->decoder != RAE_DEC_SP, v4 = (m % 4) == 0;
+    if (!a->W) return fail(RAE_E_INVALID, "W is NULL");
+    if (!a->Wb) return fail(RAE_E_INVALID, "Wb is NULL");
+    if (!a->A) return fail(RAE_E_INVALID, "A is NULL");
+    if (!a->Ab) return fail(RAE_E_INVALID, "Ab is NULL");
+    if (a->decoder != RAE_DEC_RESCAL && (!a->C1 || !a->C2))
+        return fail(RAE_E_INVALID, "C1 / C2 is NULL");
+    if (bil && !a->R3) return fail(RAE_E_INVALID, "R3 is NULL");
+    if (!a->indptr || !a->indices) return fail(RAE_E_INVALID, "indptr / indices is NULL");
+    if (!a->args1 || !a->args2) return fail(RAE_E_INVALID, "args1 / args2 is NULL");
+    if (a->nrows > 0 && !out->ents) return fail(RAE_E_INVALID, "ents is NULL");
+    if (!a->workspace) return fail(RAE_E_INVALID, "workspace is NULL");
+    if ((uintptr_t)a->workspace & 255) return fail(RAE_E_INVALID, "workspace must be 256-byte aligned");
+    if (a->workspace_bytes < (int64_t)L.total)
+        return fail(RAE_E_INVALID, "workspace_bytes is smaller than rae_topk_workspace_bytes()");
+    if (v4 && (((uintptr_t)a->W | (uintptr_t)a->Wb | (uintptr_t)a->C1 | (uintptr_t)a->C2 |
+                (uintptr_t)a->R3) & 15))
+        return fail(RAE_E_INVALID, "W / Wb / C1 / C2 / R3 must be 16-byte aligned");
+    if ((r % 4) == 0 && ((uintptr_t)a->A & 15))
+        return fail(RAE_E_INVALID, "A must be 16-byte aligned");
+    if (a->nrows == 0) return RAE_OK;         // nothing is written
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)a->workspace;
+    const size_t lds_dec = eval_dec_lds_floats(a->decoder, m, r) * 4;
+    const size_t lds_mt = eval_mt_lds_bytes(m);
+    if (lds_dec > 48 * 1024) {
+        HIPCHK(hipFuncSetAttribute(v4 ? (const void*)k_rank_build<true> : (const void*)k_rank_build<false>,
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_dec));
+    }
+    if (bil && lds_mt > 48 * 1024) {
+        HIPCHK(hipFuncSetAttribute(v4 ? (const void*)k_eval_mt<true> : (const void*)k_eval_mt<false>,
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_mt));
+    }
+    EvalArgs e;
+    e.dec = a->decoder; e.m = m; e.r = r; e.s = 0; e.alpha = a->alpha;
+    e.W = a->W; e.Wb = a->Wb; e.A = a->A; e.Ab = a->Ab; e.C1 = a->C1; e.C2 = a->C2; e.R3 = a->R3;
+    e.indptr = a->indptr; e.indices = a->indices; e.values = a->values;
+    e.args1 = a->args1; e.args2 = a->args2; e.neg1 = nullptr; e.neg2 = nullptr;
+    e.neg_stride = 0;
+    e.cap = RAE_RK_ROWCHUNK; e.r4 = eval_r4(r);
+    e.terms = (float*)(ws + L.o_terms);  // the encoder's entropy term lands here, unread
+    e.P = (float*)(ws + L.o_P); e.vpart = (float*)(ws + L.o_v); e.wpart = (float*)(ws + L.o_w);
+    for (int64_t c0 = 0; c0 < a->nrows; c0 += RAE_RK_ROWCHUNK) {
+        const int n = (int)std::min<int64_t>(RAE_RK_ROWCHUNK, a->nrows - c0);
+        e.row0 = a->row0 + c0;
+        e.n = n;
+        if (bil) {
+            const dim3 ge((unsigned)std::min(ceil_div(n, RAE_EV_NW), 65536));
+            const dim3 gm((unsigned)(eval_nbi(r) * eval_nbj(r)));
+            with_bool(v4, [&](auto V) {
+                hipLaunchKernelGGL(k_eval_enc<RAE_CV(V)>, ge, dim3(RAE_EV_BT), 0, st, e);
+                hipLaunchKernelGGL(k_eval_mt<RAE_CV(V)>, gm, dim3(RAE_EV_MTT), lds_mt, st, e);
+            });
+        }
+        RankBuild b;
+        b.Q = (float*)(ws + L.o_Q);
+        b.c = (float*)(ws + L.o_c);
+        b.u = (float*)(ws + L.o_u);
+        b.skip = (int32_t*)(ws + L.o_skip);
+        const dim3 gd((unsigned)ceil_div(n, RAE_EV_TE));
+        with_bool(v4, [&](auto V) {
+            hipLaunchKernelGGL(k_rank_build<RAE_CV(V)>, gd, dim3(RAE_EV_BT), lds_dec, st, e, b);
+        });
+        RankArgs k;
+        k.Q = b.Q; k.ldq = e.r4; k.add = b.c; k.skip = out->skip_true ? b.skip : nullptr;
+        k.A = a->A; k.Ab = a->Ab; k.n = a->n_entities; k.r = r; k.nq = 0;
+        if (const int rc = topk_launch(k, 2 * (int64_t)n, top, (rae_key64*)(ws + L.o_keys),
+                                       out->ents + 2 * c0 * top,
+                                       out->scores ? out->scores + 2 * c0 * top : nullptr, st))
+            return rc;
     }
     return RAE_OK;
 }

@@ -81,6 +81,7 @@ EXPORTS = (
     "rae_set_p2p_timeout", "rae_p2p_prologue",
     "rae_eval_workspace_bytes", "rae_eval_cost",
     "rae_rank_queries", "rae_eval_rank", "rae_rank_workspace_bytes",
+    "rae_topk_queries", "rae_eval_topk", "rae_topk_workspace_bytes",
     "rae_cluster_count", "rae_b3_metrics",
     "rae_row_keys", "rae_cluster_key_count", "rae_cluster_topk",
 )
@@ -185,6 +186,25 @@ class RaeRankOut(C.Structure):
 RAE_RK_TQ, RAE_RK_TE, RAE_RK_MAXSTRIPS, RAE_RK_QCHUNK, RAE_RK_ROWCHUNK = 128, 128, 128, 4096, 2048
 
 
+class RaeTopkArgs(C.Structure):
+    """rae_topk_args (include/rae.h): the `top` best entities of caller-given queries."""
+    _fields_ = [
+        ("Q", _P), ("ldq", C.c_int64), ("nq", C.c_int64), ("add", _P), ("skip", _P),
+        ("A", _P), ("Ab", _P), ("n_entities", C.c_int64), ("embed", C.c_int32),
+        ("top", C.c_int32), ("ents_out", _P), ("scores_out", _P),
+        ("workspace", _P), ("workspace_bytes", C.c_int64),
+    ]
+
+
+class RaeTopkOut(C.Structure):
+    """rae_topk_out (include/rae.h): the outputs of rae_eval_topk."""
+    _fields_ = [("ents", _P), ("scores", _P), ("top", C.c_int32), ("skip_true", C.c_int32)]
+
+
+# rae_topk_queries: largest `top` and the queries per launch round (csrc/rae_topk.hpp RAE_ETK_*)
+RAE_ETK_MAXTOP, RAE_ETK_QCHUNK = 32, 1024
+
+
 class RaeError(RuntimeError):
     pass
 
@@ -268,6 +288,13 @@ def load(path: str | None = None):
     lib.rae_eval_rank.restype = C.c_int
     lib.rae_rank_workspace_bytes.argtypes = [C.POINTER(RaeRankArgs), C.POINTER(RaeEvalArgs)]
     lib.rae_rank_workspace_bytes.restype = C.c_int64
+    lib.rae_topk_queries.argtypes = [C.POINTER(RaeTopkArgs), _P]
+    lib.rae_topk_queries.restype = C.c_int
+    lib.rae_eval_topk.argtypes = [C.POINTER(RaeEvalArgs), C.POINTER(RaeTopkOut), _P]
+    lib.rae_eval_topk.restype = C.c_int
+    lib.rae_topk_workspace_bytes.argtypes = [C.POINTER(RaeTopkArgs), C.POINTER(RaeEvalArgs),
+                                             C.c_int32]
+    lib.rae_topk_workspace_bytes.restype = C.c_int64
     lib.rae_cluster_count.argtypes = [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P]
     lib.rae_cluster_count.restype = C.c_int
     lib.rae_b3_metrics.argtypes = [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P]

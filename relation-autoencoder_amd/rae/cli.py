@@ -78,6 +78,18 @@ def get_command_args(argv=None, program_name="rae"):
                    help="comma-separated hits@k thresholds of --eval-rank (at most four)")
     p.add_argument("--eval-rank-rows", dest="eval_rank_rows", type=int, default=None,
                    help="rank only the first N rows of each split (default: the whole split)")
+    p.add_argument("--print-preferences", dest="print_preferences", type=int, nargs="?",
+                   const=5, default=0, metavar="N",
+                   help="after each evaluation print every induced relation's N (default 5, "
+                        "1..32) highest-scoring entities per argument slot with their scores "
+                        "(sp and rescal+sp)")
+    p.add_argument("--predict-arguments", dest="predict_arguments", type=int, default=0,
+                   metavar="ROWS",
+                   help="after the last epoch print the model's top predictions for both "
+                        "arguments of the first ROWS rows of the evaluated splits, beside the "
+                        "true argument")
+    p.add_argument("--predict-top", dest="predict_top", type=int, default=10, metavar="N",
+                   help="predictions printed per row and side by --predict-arguments (1..32)")
     p.add_argument("--cluster-eval", dest="cluster_eval", choices=["host", "device"],
                    default="host",
                    help="where the induced clusters are scored: the host evaluator, or the "
@@ -161,7 +173,10 @@ def main(argv=None):
                              cluster_eval=args.cluster_eval,
                              print_clusters=args.print_clusters, print_top=args.print_top,
                              print_by=args.print_by, eval_rank=args.eval_rank,
-                             eval_rank_ks=args.eval_rank_ks, eval_rank_rows=args.eval_rank_rows)
+                             eval_rank_ks=args.eval_rank_ks, eval_rank_rows=args.eval_rank_rows,
+                             print_preferences=args.print_preferences,
+                             predict_arguments=args.predict_arguments,
+                             predict_top=args.predict_top)
     if exchange is not None:
         ind.compile_function()
         rdist.warm_up(exchange, ind.engine.exchange_buf)

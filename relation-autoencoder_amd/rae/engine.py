@@ -1017,6 +1017,117 @@ class TrainEngine:
         _lib.check(self.lib.rae_eval_rank(C.byref(a), C.byref(o), self._stream()), "rae_eval_rank")
         return out
 
+    # ------------------------------------------------------------------ top-k entity retrieval
+    def _topk_args(self, split: DeviceSplit | None, row0: int = 0, nrows: int = 0):
+        """rae_eval_args of rae_eval_topk (the fields rae_eval_rank reads) with the engine's
+        top-k workspace, allocated once per engine for top = 32."""
+        named = self._named
+        R3 = named.get("R", named.get("C"))
+        a = _lib.RaeEvalArgs()
+        a.decoder = self.cfg.decoder
+        a.relations, a.embed = self.m, self.r
+        a.n_entities = self.cfg.n_entities
+        a.alpha = self.cfg.alpha
+        p = _lib.ptr
+        a.W, a.Wb, a.A, a.Ab = p(named["W"]), p(named["Wb"]), p(named["A"]), p(named["Ab"])
+        a.C1, a.C2, a.R3 = p(named.get("C1")), p(named.get("C2")), p(R3)
+        if split is not None:
+            a.indptr, a.indices, a.values = p(split.indptr), p(split.indices), p(split.values)
+            a.args1, a.args2 = p(split.args1), p(split.args2)
+        a.row0, a.nrows = int(row0), int(nrows)
+        if getattr(self, "_topk_ws", None) is None:      # once per engine, for both entries
+            q = _lib.RaeTopkArgs()
+            q.n_entities, q.embed = self.cfg.n_entities, self.r
+            need = max(int(self.lib.rae_topk_workspace_bytes(None, C.byref(a), _lib.RAE_ETK_MAXTOP)),
+                       int(self.lib.rae_topk_workspace_bytes(C.byref(q), None, _lib.RAE_ETK_MAXTOP)))
+            if need < 0:
+                _lib.check(-1, "rae_topk_workspace_bytes")
+            self._topk_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+        a.workspace, a.workspace_bytes = p(self._topk_ws), int(self._topk_ws.numel())
+        return a
+
+    @staticmethod
+    def _check_top(top):
+        top = int(top)
+        if not 1 <= top <= _lib.RAE_ETK_MAXTOP:
+            raise ValueError(f"top must be in [1, {_lib.RAE_ETK_MAXTOP}]")
+        return top
+
+    def topk_entities(self, Q, top: int, add=None, skip=None):
+        """The `top` best-scoring entities of every row of Q ((nq, r) fp32) against the engine's
+        A / Ab (rae_topk_queries): score <Q[q], A[e]> + add[q] + Ab[e], entity skip[q] left out.
+        Returns (ents int32, scores fp32), both (nq, top), ordered by score descending then
+        entity ascending, padded with (-1, -inf).  Queued on the current stream, no host
+        synchronisation.  Touches no parameter, accumulator, plan state, cursor, negative or RNG;
+        partitioned update with stale rows: gathers the parameters first (a collective)."""
+        top = self._check_top(top)
+        if self.stale(accumulators=False):
+            self.sync_replicas(accumulators=False)
+        Q = torch.as_tensor(Q, dtype=torch.float32, device=self.device)
+        if Q.dim() != 2 or Q.shape[1] != self.r:
+            raise ValueError(f"Q must be (nq, {self.r}), got {tuple(Q.shape)}")
+        nq = int(Q.shape[0])
+        ldq = (self.r + 3) & ~3
+        if ldq != self.r or not Q.is_contiguous() or Q.data_ptr() % 16:
+            Qp = torch.zeros((nq, ldq), dtype=torch.float32, device=self.device)
+            Qp[:, :self.r] = Q
+            Q = Qp
+        vec = lambda x, dt: None if x is None else torch.as_tensor(
+            x, device=self.device).to(dt).contiguous().reshape(nq)
+        add, skip = vec(add, torch.float32), vec(skip, torch.int32)
+        e = self._topk_args(None)
+        ents = torch.empty((nq, top), dtype=torch.int32, device=self.device)
+        scores = torch.empty((nq, top), dtype=torch.float32, device=self.device)
+        p = _lib.ptr
+        a = _lib.RaeTopkArgs()
+        a.Q, a.ldq, a.nq = p(Q), ldq, nq
+        a.add, a.skip = p(add), p(skip)
+        a.A, a.Ab = e.A, e.Ab
+        a.n_entities, a.embed, a.top = self.cfg.n_entities, self.r, top
+        a.ents_out, a.scores_out = p(ents), p(scores)
+        a.workspace, a.workspace_bytes = e.workspace, e.workspace_bytes
+        _lib.check(self.lib.rae_topk_queries(C.byref(a), self._stream()), "rae_topk_queries")
+        return ents, scores
+
+    def predict_arguments(self, split: DeviceSplit, row0: int = 0, nrows: int | None = None,
+                          top: int = 10, skip_true: bool = False):
+        """The `top` entities the model puts in each argument slot of rows [row0, row0+nrows) of
+        `split`, given the other argument and the induced relation (rae_eval_topk; the scores are
+        rae_eval_rank's).  Returns (ents int32, scores fp32), both (nrows, 2, top); skip_true
+        leaves the row's true argument out.  Queued on the current stream.  Touches no parameter,
+        accumulator, plan state, cursor, negative or RNG; partitioned update with stale rows:
+        gathers the parameters first (a collective, like rank)."""
+        top = self._check_top(top)
+        if self.stale(accumulators=False):
+            self.sync_replicas(accumulators=False)
+        row0 = int(row0)
+        nrows = split.N - row0 if nrows is None else int(nrows)
+        if row0 < 0 or nrows < 0 or row0 + nrows > split.N:
+            raise IndexError(f"rows [{row0}, {row0 + nrows}) out of the split's {split.N}")
+        a = self._topk_args(split, row0, nrows)
+        ents = torch.empty((nrows, 2, top), dtype=torch.int32, device=self.device)
+        scores = torch.empty((nrows, 2, top), dtype=torch.float32, device=self.device)
+        o = _lib.RaeTopkOut()
+        o.ents, o.scores, o.top, o.skip_true = _lib.ptr(ents), _lib.ptr(scores), top, int(skip_true)
+        _lib.check(self.lib.rae_eval_topk(C.byref(a), C.byref(o), self._stream()), "rae_eval_topk")
+        return ents, scores
+
+    def relation_preferences(self, top: int = 10):
+        """The selectional preferences of every induced relation: for relation k and slot t the
+        `top` entities e with the highest SP score <A[e], C_t[:, k]> + Ab[e] ('sp' and
+        'rescal+sp'; the queries are the columns of C1 / C2).  Returns (ents int32, scores fp32),
+        both (2, m, top).  'rescal' has no per-relation vector: ValueError."""
+        top = self._check_top(top)
+        named = self._named
+        if "C1" not in named or "C2" not in named:
+            raise ValueError("relation_preferences needs the selectional-preference matrices "
+                             "C1 / C2 ('sp' or 'rescal+sp'); 'rescal' has no per-relation vector")
+        if self.stale(accumulators=False):
+            self.sync_replicas(accumulators=False)
+        Q = torch.cat([named["C1"].detach().t(), named["C2"].detach().t()]).contiguous()
+        ents, scores = self.topk_entities(Q, top)
+        return ents.reshape(2, self.m, top), scores.reshape(2, self.m, top)
+
     # ------------------------------------------------------------------ cluster evaluation
     def _gold_dev(self, split: DeviceSplit, gold_index):
         """The gold ids (int32, split.N; -1 past the index's rows) and sizes (int64) of

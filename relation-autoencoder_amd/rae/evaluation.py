@@ -325,3 +325,76 @@ def format_cluster_profiles(keys, counts, names):
         items = [(names[int(k)], int(n)) for k, n in zip(keys[c], counts[c]) if k >= 0]
         lines.append(f"{c} " + " ".join(map(str, items)))
     return lines
+
+
+# ------------------------------------------------------------------ top-k entity retrieval
+def topk_from_scores(g, top, skip=None):
+    """(ents, scores) of rae_topk_queries from the (nq, n) score matrix g: per row the entities
+    other than skip[q] (skip outside [0, n): nothing is skipped) whose score is not NaN, ordered by
+    score descending, then entity ascending, cut to `top` and padded with (-1, -inf).  -0.0 is
+    +0.0, in the order and in the output.  ents int32 (nq, top), scores g's dtype."""
+    g = np.array(g, copy=True)
+    if g.dtype.kind != "f":
+        g = g.astype(np.float64)
+    nq, n = g.shape
+    g = np.where(g == 0, g.dtype.type(0), g)                  # -0 -> +0
+    ents = np.full((nq, top), -1, dtype=np.int32)
+    scores = np.full((nq, top), -np.inf, dtype=g.dtype)
+    sk = None if skip is None else np.asarray(skip).astype(np.int64)
+    for q in range(nq):
+        row = g[q]
+        keep = ~np.isnan(row)
+        if sk is not None and 0 <= sk[q] < n:
+            keep[sk[q]] = False
+        cand = np.flatnonzero(keep)
+        order = cand[np.lexsort((cand, -row[cand]))][:top]
+        ents[q, :order.shape[0]] = order
+        scores[q, :order.shape[0]] = row[order]
+    return ents, scores
+
+
+def entity_name(names, e):
+    """The string of entity id e: names[e] of a mapping or sequence (DatasetManager.id2Arg), or
+    the id itself when there is none."""
+    e = int(e)
+    if names is not None:
+        try:
+            s = names[e]
+            if s is not None:
+                return str(s)
+        except (KeyError, IndexError):
+            pass
+    return str(e)
+
+
+def _topk_pairs(ents, scores, names):
+    # %.9g round-trips a float32
+    return ["{}:{:.9g}".format(entity_name(names, e), float(s))
+            for e, s in zip(ents, scores) if e >= 0]
+
+
+def format_relation_preferences(ents, scores, names=None):
+    """ents / scores (2, m, top) of TrainEngine.relation_preferences -> one line per relation and
+    slot, tab-separated: 'preferences', the relation id, the slot (1 or 2), then entity:score
+    pairs, best first (padding is not printed)."""
+    ents, scores = np.asarray(ents), np.asarray(scores)
+    lines = []
+    for k in range(ents.shape[1]):
+        for t in range(2):
+            lines.append("\t".join(["preferences", str(k), str(t + 1)] +
+                                   _topk_pairs(ents[t, k], scores[t, k], names)))
+    return lines
+
+
+def format_argument_predictions(ents, scores, true, names=None, row0=0):
+    """ents / scores (nrows, 2, top) of TrainEngine.predict_arguments, true (nrows, 2) the rows'
+    arguments -> one line per row and side, tab-separated: 'predictions', the row, the side (1 or
+    2), the true argument, then entity:score pairs, best first."""
+    ents, scores, true = np.asarray(ents), np.asarray(scores), np.asarray(true)
+    lines = []
+    for b in range(ents.shape[0]):
+        for t in range(2):
+            lines.append("\t".join(["predictions", str(row0 + b), str(t + 1),
+                                    entity_name(names, true[b, t])] +
+                                   _topk_pairs(ents[b, t], scores[b, t], names)))
+    return lines

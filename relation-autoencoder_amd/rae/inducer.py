@@ -14,7 +14,8 @@ import torch
 from .data import SPLIT_LABELS
 from .engine import DeviceSplit, TrainEngine
 from .evaluation import (GoldIndex, KeyIndex, construct_split_evaluator,
-                         format_cluster_profiles, key_table, row_keys, topk_from_table)
+                         format_argument_predictions, format_cluster_profiles,
+                         format_relation_preferences, key_table, row_keys, topk_from_table)
 from .model import OieModelFunctions, _as_bool, make_optimizer
 from .negatives import NegativeExampleGenerator
 
@@ -77,7 +78,14 @@ class ReconstructInducer:
                  index_overlap=True, p2p_cross_device=False, p2p_timeout=5.0,
                  eval_cost=False, eval_seed=None, cluster_eval="host", print_clusters="off",
                  print_top=5, print_by="trigger", eval_rank=False, eval_rank_ks=(1, 10, 100),
-                 eval_rank_rows=None):
+                 eval_rank_rows=None, print_preferences=0, predict_arguments=0, predict_top=10):
+        if not 0 <= int(print_preferences) <= 32:
+            raise ValueError("print_preferences must be in [0, 32] (0: off)")
+        if int(predict_arguments) < 0 or not 1 <= int(predict_top) <= 32:
+            raise ValueError("predict_arguments must be >= 0 and predict_top in [1, 32]")
+        if int(print_preferences) and decoder_model == "rescal":
+            raise ValueError("print_preferences needs the selectional-preference matrices "
+                             "('sp' or 'rescal+sp')")
         if cluster_eval not in ("host", "device"):
             raise ValueError("cluster_eval must be 'host' or 'device'")
         if print_clusters not in ("off", "host", "device"):
@@ -142,6 +150,13 @@ class ReconstructInducer:
             raise ValueError("eval_rank_ks: at most four thresholds, each >= 1")
         self.eval_rank_rows = None if eval_rank_rows is None else int(eval_rank_rows)
         self.rank_metrics = {s: [] for s in SPLIT_LABELS}
+        # print_preferences: after each epoch's evaluation learn() prints, per induced relation
+        # and argument slot, the N highest-scoring entities (TrainEngine.relation_preferences);
+        # predict_arguments: after the last epoch, the predict_top best entities for both
+        # arguments of the first ROWS rows of the evaluated splits (TrainEngine.predict_arguments)
+        self.print_preferences = int(print_preferences)
+        self.predict_arguments = int(predict_arguments)
+        self.predict_top = int(predict_top)
         # cluster_eval: where learn() scores the induced clusters -- "host": the label download
         # and the Python sets of the reference (get_clusters_sets + SingleLabelClusterEvaluation);
         # "device": the contingency table and B^3 on the GPU (TrainEngine.cluster_metrics), same
@@ -318,7 +333,39 @@ class ReconstructInducer:
             if self.eval_rank:
                 for split in (SPLIT_LABELS[:1] if self._mode() == 1 else SPLIT_LABELS[1:]):
                     self.evaluate_rank(split, verbose=verbose)
+            # computed whatever `verbose` is, like evaluate_rank: the engine calls may gather stale
+            # replicas (a collective), so every rank makes them; only the printing is optional
+            if self.print_preferences:
+                lines = self.relation_preference_lines()
+                if verbose:
+                    print("\n".join(lines))
+        if self.predict_arguments:
+            for split in (SPLIT_LABELS[:1] if self._mode() == 1 else SPLIT_LABELS[1:]):
+                lines = self.argument_prediction_lines(split)
+                if verbose:
+                    print("\n".join(lines))
         return self.train_errors
+
+    def relation_preference_lines(self):
+        """print_preferences' lines at the current parameters: one per relation and slot."""
+        if not self._check_for_compiled_functions():
+            self.compile_function()
+        ents, scores = self.engine.relation_preferences(self.print_preferences or 5)
+        return format_relation_preferences(ents.cpu().numpy(), scores.cpu().numpy(),
+                                           getattr(self.data, "id2Arg", None))
+
+    def argument_prediction_lines(self, split):
+        """predict_arguments' lines for the first predict_arguments rows of `split`: a header,
+        then one line per row and side."""
+        if not self._check_for_compiled_functions():
+            self.compile_function()
+        ds = self._dev_split[split]
+        nrows = max(0, min(ds.N, self.predict_arguments))
+        ents, scores = self.engine.predict_arguments(ds, 0, nrows, top=self.predict_top)
+        sp = self.data.split[split]
+        true = np.stack([np.asarray(sp.args1[:nrows]), np.asarray(sp.args2[:nrows])], axis=1)
+        return ["{} predictions ({} rows)".format(split, nrows)] + format_argument_predictions(
+            ents.cpu().numpy(), scores.cpu().numpy(), true, getattr(self.data, "id2Arg", None))
 
     def evaluate_cost(self, split, verbose=True):
         """The forward-only objective of the whole `split` at the current parameters, against
