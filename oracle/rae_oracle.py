@@ -184,7 +184,7 @@ def _decoder_forward_backward(decoder, p, P, H, e1, e2, neg1, neg2, D, bf16=Fals
 
     bf16 (bilinear decoders only): emulate rae_config.mfma_bf16 -- the three R contractions
     take bf16-rounded operands (fp32 / here float64 accumulation), exactly where the MI355X
-    kernels round: M = P.R (k_bil_mt: bf16 P and R), dP = sum_ij U_ij R_ij (U = x a2^T + a1 y^T
+    kernels round: M = P.R (k_bil_mt: bf16 P and R; m <= 128 only, fp32 above), dP = sum_ij U_ij R_ij (U = x a2^T + a1 y^T
     formed in fp32, then rounded), dR = sum_b P_b U_b (U formed from bf16 copies of x, a1, a2,
     y, then rounded; P bf16).  Not the reference's arithmetic: it measures how far bf16
     operands alone move a trajectory, which is what the bf16 path's tolerance is derived from
@@ -239,7 +239,10 @@ def _decoder_forward_backward(decoder, p, P, H, e1, e2, neg1, neg2, D, bf16=Fals
         a2 = A[e2]
         # M_b = sum_k P_bk R[:,:,k]  (Bilinear.py:33 / BilinearPlusSP.py:37) as one GEMM
         Rb = (bf16_round(Rk) if bf16 else Rk).reshape(r_ * r_, -1)
-        M = ((bf16_round(P) if bf16 else P) @ Rb.T).reshape(l, r_, r_)
+        # the M-tile passes take bf16 operands up to m = 128 (rae_plan.hpp mt_ok: k_bil_mt's bf16
+        # blocks); above that the plan forms M with exact fp32 MFMAs and only dP / dR round
+        bf16_m = bf16 and P.shape[1] <= 128
+        M = ((bf16_round(P) @ Rb.T) if bf16_m else (P @ Rk.reshape(r_ * r_, -1).T)).reshape(l, r_, r_)
         Ma2 = np.einsum("bij,bj->bi", M, a2)        # M a2
         MTa1 = np.einsum("bij,bi->bj", M, a1)       # M^T a1
         one = np.einsum("bi,bi->b", a1, Ma2)        # Bilinear.py:58-59

@@ -12,7 +12,8 @@ MODE
              identical AdaGrad step.  Each rank saves its params.
   gpu        the real HIP path with world_size 2: both ranks share cuda:0, the exchange
              records go through gloo (host-staged), eager steps.  Each rank saves its
-             params and per-batch costs.
+             params, AdaGrad accumulators (acc_<name>) and per-batch costs.  Optional trailing
+             arguments: lambda1, lambda2, optimizer (defaults 0, 0, adagrad).
   gpu_c3     the same at BASELINE config 3's full size with global batch L = 800 (2 x 400);
              argument 3: the data-parallel update ("replicated" | "partitioned").
   oracle_part  the row-owner partitioned update's protocol on the float64 oracle.
@@ -207,7 +208,8 @@ def run_sync_rows(out):
 
 
 def run_gpu(out, decoder, dp_update="replicated", dense="auto", priv="auto", index_window=0,
-            xchg="collective", graph_chunk=1, vocab="small"):
+            xchg="collective", graph_chunk=1, vocab="small", lambda1=0.0, lambda2=0.0,
+            optimizer="adagrad"):
     from rae import dist as rdist
     from rae.inducer import ReconstructInducer
     ws, rk = dist.get_world_size(), dist.get_rank()
@@ -217,8 +219,8 @@ def run_gpu(out, decoder, dp_update="replicated", dense="auto", priv="auto", ind
     m, r, s, l = DP_SHAPE["m"], DP_SHAPE["r"], DP_SHAPE["s"], DP_SHAPE["l"]
     ex = rdist.make_exchange(ws, rk)
     ind = ReconstructInducer(data, gold, np.random.RandomState(2), DP_SHAPE["epochs"], 0.1, l, r,
-                             m, s, 0.0, 0.0, "adagrad", "dp", decoder, False, True, False, 1.0,
-                             device=dev, world_size=ws, rank=rk, exchange=ex,
+                             m, s, lambda1, lambda2, optimizer, "dp", decoder, False, True, False,
+                             1.0, device=dev, world_size=ws, rank=rk, exchange=ex,
                              graph_chunk=graph_chunk, dp_update=dp_update,
                              kernel_forms=dict({"dp_dense": dense} if decoder == "sp" else {},
                                                priv_rows=priv, dp_xchg=xchg),
@@ -232,6 +234,9 @@ def run_gpu(out, decoder, dp_update="replicated", dense="auto", priv="auto", ind
         assert ind.engine.kernel_forms_in_use()["priv_rows"] == priv
     ind.engine.sync_replicas()
     params = {k: v.detach().cpu().double().numpy() for k, v in ind.modelFunc.named_params().items()}
+    if ind.optimizer.accumulator is not None:      # AdaGrad state, gathered like the parameters
+        for k, v in zip(ind.modelFunc.param_names, ind.optimizer.accumulator):
+            params["acc_" + k] = v.detach().cpu().numpy()
     tag = dp_update if xchg == "collective" else f"{dp_update}_{xchg}"
     if vocab != "small":
         tag += "_" + vocab
@@ -479,7 +484,10 @@ def main():
                     int(sys.argv[7]) if len(sys.argv) > 7 else 0,
                     sys.argv[8] if len(sys.argv) > 8 else "collective",
                     int(sys.argv[9]) if len(sys.argv) > 9 else 1,
-                    sys.argv[10] if len(sys.argv) > 10 else "small")
+                    sys.argv[10] if len(sys.argv) > 10 else "small",
+                    float(sys.argv[11]) if len(sys.argv) > 11 else 0.0,
+                    float(sys.argv[12]) if len(sys.argv) > 12 else 0.0,
+                    sys.argv[13] if len(sys.argv) > 13 else "adagrad")
         elif mode == "gpu_c3":
             run_gpu_c3(out, dp_update=dec if dec != "sp" else "replicated",
                        heavy_chunk=sys.argv[4] if len(sys.argv) > 4 else "auto")

@@ -37,15 +37,25 @@ def _launch(args, timeout=300, nproc=2):
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
 
 
-def _single_process_oracle(decoder, lambda1=0.0, ws=2):
+def _single_process_oracle(decoder, lambda1=0.0, ws=2, lambda2=0.0, optimizer="adagrad"):
     data, _ = _dataset()
     sp_ = data.split["train"]
     L = ws * DP_SHAPE["l"]
     tr = O.OracleTrainer(decoder, sp_.xFeats, sp_.args1, sp_.args2, data.negSamplingCum,
                          np.random.RandomState(2), DP_SHAPE["m"], DP_SHAPE["r"], DP_SHAPE["s"], L,
-                         lr=0.1, alpha=1.0, lambda1=lambda1)
+                         lr=0.1, alpha=1.0, lambda1=lambda1, lambda2=lambda2, optimizer=optimizer)
     costs = np.concatenate([tr.epoch()[0] for _ in range(DP_SHAPE["epochs"])])
     return tr, costs
+
+
+def _assert_accumulators_equal(gp, gr):
+    """The partitioned ranks' AdaGrad accumulators (after the final gather) == the replicated
+    run's, bit for bit."""
+    acc = [k for k in gr.files if k.startswith("acc_")]
+    assert acc
+    for k in acc:
+        for g in gp:
+            np.testing.assert_array_equal(g[k], gr[k], err_msg=k)
 
 
 def test_exchange_all_gather_gloo(tmp_path):
@@ -103,19 +113,31 @@ def test_partitioned_update_equals_global_batch(tmp_path, decoder, ws):
         np.testing.assert_allclose(rs[0][k], v, rtol=1e-9, atol=1e-11, err_msg=k)
 
 
+_DP_PLAIN = [("sp", 2, "auto"), ("rescal", 2, "auto"), ("rescal+sp", 2, "auto"), ("sp", 4, "auto"),
+             ("sp", 8, "auto"), ("rescal+sp", 8, "auto"), ("sp", 2, "partials"),
+             ("sp", 4, "partials"), ("sp", 8, "partials")]
+# with a regulariser (every rank's dense W sweep, the L1 / L2 partials) and with SGD
+_DP_OPTIONS = [("sp", 2, "auto", dict(lambda1=0.01), "l1"),
+               ("rescal+sp", 2, "auto", dict(lambda1=0.01, lambda2=0.1), "l1l2"),
+               ("rescal", 2, "auto", dict(optimizer="sgd"), "sgd")]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("decoder,ws,dense", [("sp", 2, "auto"), ("rescal", 2, "auto"),
-                                              ("rescal+sp", 2, "auto"), ("sp", 4, "auto"),
-                                              ("sp", 8, "auto"), ("rescal+sp", 8, "auto"),
-                                              ("sp", 2, "partials"), ("sp", 4, "partials"),
-                                              ("sp", 8, "partials")])
-def test_gpu_ranks_match_global_batch(built_lib, cuda_dev, tmp_path, decoder, ws, dense):
+@pytest.mark.parametrize("decoder,ws,dense,hp", [
+    pytest.param(*c, {}, id="-".join(str(x) for x in c)) for c in _DP_PLAIN] + [
+    pytest.param(*c[:3], c[3], id="-".join(str(x) for x in c[:3]) + "-" + c[4])
+    for c in _DP_OPTIONS])
+def test_gpu_ranks_match_global_batch(built_lib, cuda_dev, tmp_path, decoder, ws, dense, hp):
     """The HIP path on `ws` ranks sharing the GPU (replicated update) == the oracle at the
-    global batch, replicas bit-identical; SP both ways of moving the dense decoder-matrix
-    gradients (rae.h RAE_DPDENSE_*: each rank's partials, or -- auto at this shape -- every
-    example's dw1 / dw2 in the records)."""
-    _launch(["gpu", str(tmp_path), decoder, "replicated", dense], nproc=ws)
-    tr, costs = _single_process_oracle(decoder, ws=ws)
+    global batch, replicas bit-identical (AdaGrad accumulators included); SP both ways of moving
+    the dense decoder-matrix gradients (rae.h RAE_DPDENSE_*: each rank's partials, or -- auto at
+    this shape -- every example's dw1 / dw2 in the records); with a regulariser and with SGD."""
+    extra = []
+    if hp:
+        extra = ["auto", "0", "collective", "1", "small", str(hp.get("lambda1", 0.0)),
+                 str(hp.get("lambda2", 0.0)), hp.get("optimizer", "adagrad")]
+    _launch(["gpu", str(tmp_path), decoder, "replicated", dense] + extra, nproc=ws)
+    tr, costs = _single_process_oracle(decoder, ws=ws, **hp)
     gs = [np.load(tmp_path / f"gpu_replicated_{decoder}_{k}.npz") for k in range(ws)]
     np.testing.assert_allclose(gs[0]["costs"], costs, rtol=2e-5, atol=2e-5)
     for k, v in tr.params.items():
@@ -123,6 +145,11 @@ def test_gpu_ranks_match_global_batch(built_lib, cuda_dev, tmp_path, decoder, ws
             np.testing.assert_array_equal(gs[0][k], gk[k])    # bit-identical replicas
         err = np.abs(gs[0][k] - v)
         assert np.all(err <= 2e-4 + 2e-3 * np.abs(v)), f"{k}: max err {err.max():.3e}"
+    acc = [k for k in gs[0].files if k.startswith("acc_")]
+    assert bool(acc) == (hp.get("optimizer", "adagrad") == "adagrad")
+    for k in acc:
+        for gk in gs[1:]:
+            np.testing.assert_array_equal(gs[0][k], gk[k], err_msg=k)
 
 
 @pytest.mark.gpu
@@ -157,6 +184,7 @@ def test_gpu_partitioned_update(built_lib, cuda_dev, tmp_path, decoder, ws, dens
         np.testing.assert_array_equal(gp[0][k], gr[k])
         err = np.abs(gp[0][k] - v)
         assert np.all(err <= 2e-4 + 2e-3 * np.abs(v)), f"{k}: max err {err.max():.3e}"
+    _assert_accumulators_equal(gp, gr)
 
 
 @pytest.mark.gpu
@@ -340,3 +368,4 @@ def test_gpu_p2p_exchange(built_lib, cuda_dev, tmp_path, decoder, ws, graph_chun
         np.testing.assert_array_equal(gp[0][k], gr[k])
         err = np.abs(gp[0][k] - v)
         assert np.all(err <= 2e-4 + 2e-3 * np.abs(v)), f"{k}: max err {err.max():.3e}"
+    _assert_accumulators_equal(gp, gr)

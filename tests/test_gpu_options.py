@@ -1,0 +1,231 @@
+"""One training step under every optimiser / regulariser option, the device's state against the
+host references of tests/_grad_ref.py (needs an MI355X).
+
+The shape-varying tests of this suite all train with AdaGrad, lambda = 0, alpha = 1, ext_reg and
+binary features, and see the gradient only through AdaGrad's normalised step.  Here, per
+(shape, option) case and for each of three batches: the generic parameters are copied into the
+inducer's tensors (as a checkpoint load does), the accumulators zeroed, exactly that batch is
+run, and
+
+  cost       within COST_RTOL of the float64 oracle's (the L1 / L2 sums live here);
+  AdaGrad    the gradient extracted from the state (sqrt(acc), sign of p0 - p1) has
+             rho(g_gpu, g64) <= 16 max(rho(g_host32, g64), 2^-20) per tensor, and p1 is the
+             AdaGrad step of that gradient to 8 * 2^-24 (|p0| + lr);
+  SGD        (lr = 1) |p1 - (p0 - lr g64)| <= lr (row tolerance) + 2^-23 |p1|;
+  untouched  rows whose gradient is exactly zero keep p1 bit-identical to p0 and acc == 0;
+  bf16       test_gpu_fullscale.check_bf16's rule on rho: rho(gpu, exact) <= 1.25 rho(emu, exact)
+             + t and rho(gpu, emu) <= 0.25 rho(emu, exact) + t, t the fp32 tolerance above (the
+             AdaGrad sign rule is applied against each reference with that reference's bound);
+  forms      kernel_forms_in_use() shows the intended form.
+
+The yardstick is the float32 host's distance from float64 at the same parameters (measured
+7e-8 ... 1e-5; up to 8.8e-4 on W where P saturates), not the code under test; the factor 16 covers __expf / __logf / rcp argument
+scaling (~|x| 2^-24, |x| <~ 12) and the MFMA / wave-tree summation orders, the floor 2^-20 keeps a
+near-exact host vector from setting an impossible bound.  Every measured ratio
+rho_gpu / max(rho_host32, 2^-20) is printed ("RATIO ..."); profiles/options_grad_check.txt keeps
+the table.
+
+The trajectory test at the end runs whole epochs (graph-captured, graph_chunk = 2) under the
+regulariser with both optimisers: state carried between steps (the dense W scratch re-zeroed,
+the L1 / L2 partial slots reused, SGD steps composing).
+"""
+import numpy as np
+import pytest
+
+import _grad_ref as G
+
+pytestmark = pytest.mark.gpu
+
+COST_RTOL = 2e-5            # tests/test_gpu_train.py
+BF16_EXACT_FACTOR, BF16_EMU_FACTOR = 1.25, 0.25     # tests/test_gpu_fullscale.py
+
+
+def _expected_forms(c):
+    reg = c["l1"] != 0.0 or c["l2"] != 0.0
+    want = dict(c["want"])
+    want.setdefault("priv_rows", "on" if (not reg and 2 + 2 * c["s"] <= 64) else "off")
+    want.setdefault("heavy_chunk", "off")
+    if c["dec"] != "sp":
+        want.setdefault("bil_dp", "mtile" if (c["bf16"] and c["m"] <= 128) else "strided")
+    return want
+
+
+def _inducer(c, dev, forms=None):
+    from rae.inducer import ReconstructInducer
+    data, neg1, neg2 = G.case_dataset(c)
+    kf = dict(c["forms"])
+    kf.update(forms or {})
+    ind = ReconstructInducer(data, {"train": {}}, np.random.RandomState(2), 1, c["lr"], c["l"],
+                             c["r"], c["m"], c["s"], c["l1"], c["l2"], c["opt"], "options",
+                             c["dec"], False, c["ext_reg"], False, c["alpha"], device=dev,
+                             graph_chunk=1, mfma_bf16=c["bf16"], kernel_forms=kf)
+    ind.compile_function()
+    return ind, neg1, neg2
+
+
+def _one_step_states(c, dev, forms=None, per_call=False):
+    """[(cost, p1, acc1)] of the three batches, each run alone from the generic parameters and
+    zero accumulators; the resolved kernel forms."""
+    import torch
+    ind, neg1, neg2 = _inducer(c, dev, forms)
+    eng = ind.engine
+    named = ind.modelFunc.named_params()
+    accs = dict(zip(ind.modelFunc.param_names, ind.optimizer.accumulator or []))
+    p0 = G.generic_params(c)
+    if not per_call:
+        eng.set_epoch_negatives(neg1, neg2)
+    out = []
+    for b in range(G.N_BATCHES):
+        for k, v in named.items():
+            v.copy_(torch.as_tensor(p0[k]))
+        for v in accs.values():
+            v.zero_()
+        if per_call:        # func['train'](batch, neg1, neg2): the per-call ABI
+            cols = slice(b * c["l"], (b + 1) * c["l"])
+            cost = ind.func["train"](b, neg1[:, cols], neg2[:, cols])
+        else:
+            eng.run(b, 1)
+            torch.cuda.synchronize()
+            eng.check()
+            cost = float(eng.costs[b].item())
+        out.append((cost, {k: v.detach().cpu().numpy().copy() for k, v in named.items()},
+                    {k: v.detach().cpu().numpy().copy() for k, v in accs.items()}))
+    forms_used = eng.kernel_forms_in_use()
+    ind._drop_engine()
+    return out, forms_used
+
+
+def _check_step(c, b, cost, p1, acc, tag, bad):
+    """The assertions of one batch; failures are appended to `bad` (so every ratio of the case
+    is printed before the test fails)."""
+    ref = G.references(c, b)
+    p0 = G.generic_params(c)
+    lr = c["lr"]
+    want = ref["cost64"]
+    if c["bf16"]:
+        dc = abs(ref["cost_emu"] - want)
+        ok = (abs(cost - want) <= BF16_EXACT_FACTOR * dc + COST_RTOL * abs(want) and
+              abs(cost - ref["cost_emu"]) <= BF16_EMU_FACTOR * dc + COST_RTOL * abs(want))
+    else:
+        ok = abs(cost - want) <= COST_RTOL * max(1.0, abs(want))
+    print(f"COST {tag} b{b} gpu {cost:.9g} oracle {want:.9g} rel {abs(cost - want) / abs(want):.2e}")
+    if not ok:
+        bad.append(f"b{b} cost {cost!r} oracle {want!r}")
+    for k, g64 in ref["g64"].items():
+        t = G.tolerance(ref["rho32"][k])
+        emu = ref["rho_emu"][k] if c["bf16"] else 0.0
+        tol_exact = BF16_EXACT_FACTOR * emu + t
+        a0 = p0[k].astype(np.float64)
+        a1 = p1[k].astype(np.float64)
+        rm = G.row_max(g64)
+        # rows with an exactly zero gradient: never written
+        zero = rm == 0.0
+        if not np.array_equal(p1[k][zero], p0[k][zero]):
+            bad.append(f"b{b} {k}: an untouched row changed")
+        if c["opt"] == "adagrad":
+            ak = acc[k].astype(np.float64)
+            if np.any(ak[zero] != 0.0):
+                bad.append(f"b{b} {k}: accumulator of an untouched row is not zero")
+            g = G.extract_adagrad(a0, a1, ak, g64, tol_exact)
+            # the step's size from the accumulator alone (its sign is in g, checked by rho)
+            step = lr * np.sqrt(ak) / (np.sqrt(ak) + 1e-6)
+            off = np.abs(np.abs(a0 - a1) - step)
+            if not np.all(off <= 8 * 2.0 ** -24 * (np.abs(a0) + lr)):
+                bad.append(f"b{b} {k}: p1 is not the AdaGrad step of sqrt(acc): {off.max():.3e}")
+            slack = 0.0
+        else:
+            g = (a0 - a1) / lr
+            slack = 2.0 ** -23 * np.abs(a1) / lr      # the one rounding of p1
+        r_gpu = _rho_slack(g, g64, slack)
+        ratio = r_gpu / max(ref["rho32"][k], G.FLOOR)
+        line = (f"RATIO {tag} b{b} {k:2s} rho_gpu {r_gpu:.3e} rho_host32 {ref['rho32'][k]:.3e} "
+                f"ratio {ratio:.3f}")
+        if c["bf16"]:
+            if c["opt"] == "adagrad":       # the sign rule against this reference's own tolerance
+                g = G.extract_adagrad(a0, a1, ak, ref["g_emu"][k], BF16_EMU_FACTOR * emu + t)
+            r_emu = _rho_slack(g, ref["g_emu"][k], slack)
+            line += f" rho_emu {emu:.3e} rho_gpu_emu {r_emu:.3e}"
+            if not r_emu <= BF16_EMU_FACTOR * emu + t:
+                bad.append(f"b{b} {k}: rho(gpu, emu) {r_emu:.3e} > 0.25 * {emu:.3e} + {t:.3e}")
+        print(line)
+        if not r_gpu <= tol_exact:
+            bad.append(f"b{b} {k}: rho(gpu, f64) {r_gpu:.3e} > {tol_exact:.3e} "
+                       f"(host32 {ref['rho32'][k]:.3e}, ratio {ratio:.2f})")
+
+
+def _rho_slack(x, g, slack):
+    """rho(x, g) with a per-element allowance `slack` taken off |x - g| first (SGD: the rounding
+    of p1, which is not the gradient's error)."""
+    if np.isscalar(slack):
+        return G.rho(x, g)
+    err = np.maximum(np.abs(x - g) - slack, 0.0)
+    zero = G.row_max(g) == 0.0
+    if np.any(np.asarray(x)[zero] != 0.0):
+        return float("inf")
+    return G.rho(g + err, g)
+
+
+VARIANTS = [(s, o, None, False) for s, o in G.CASES] + [
+    ("S1", "O0", "on", False), ("S1", "O0", "off", False),      # private rows on / off
+    ("S3", "O1", None, True), ("H1", "O4", None, True)]          # func['train'], the per-call ABI
+
+
+def _vid(v):
+    return f"{v[0]}-{v[1]}" + (f"-priv_{v[2]}" if v[2] else "") + ("-percall" if v[3] else "")
+
+
+@pytest.mark.parametrize("variant", VARIANTS, ids=[_vid(v) for v in VARIANTS])
+def test_one_step_state_vs_reference(built_lib, cuda_dev, variant):
+    shape, option, priv, per_call = variant
+    c = G.case_config(shape, option)
+    forms = {"priv_rows": priv} if priv else None
+    states, used = _one_step_states(c, cuda_dev, forms, per_call)
+    want = _expected_forms(c)
+    if priv:
+        want["priv_rows"] = priv
+    assert {k: used[k] for k in want} == want, used
+    bad = []
+    for b, (cost, p1, acc) in enumerate(states):
+        _check_step(c, b, cost, p1, acc, _vid(variant), bad)
+    assert not bad, "\n".join(bad)
+
+
+# --------------------------------------------------------------------------------------------
+# short trajectories: state carried between steps
+# --------------------------------------------------------------------------------------------
+def _trajectory_oracle(c, data, bf16=False):
+    from test_gpu_train import _oracle_trajectory
+    tr, costs = _oracle_trajectory(c["dec"], data, 2, c["m"], c["r"], c["s"], c["l"], 1,
+                                   lr=c["lr"], optimizer=c["opt"], lambda1=c["l1"],
+                                   lambda2=c["l2"], ext_reg=c["ext_reg"], alpha=c["alpha"],
+                                   bf16=bf16)
+    return costs[0], tr.params
+
+
+@pytest.mark.parametrize("shape", ["S1", "B4", "H1"])
+@pytest.mark.parametrize("option", ["O1", "O4"])
+def test_epoch_under_options_vs_oracle(built_lib, cuda_dev, shape, option):
+    """One epoch (3 steps) with learn() from the reference initialisation, graph-captured with
+    graph_chunk = 2, against the oracle's trajectory under the same options at the suite's
+    tolerances (costs COST_RTOL, parameters 2e-4 + 2e-3 |p|); bf16 plans by check_bf16."""
+    from rae.inducer import ReconstructInducer
+    from test_gpu_fullscale import check_bf16
+    from test_gpu_train import _assert_params_close, _params
+    c = G.case_config(shape, option)
+    c["lr"] = 0.1               # a trajectory: the reference's learning rate for both optimisers
+    data, _, _ = G.case_dataset(c)
+    ind = ReconstructInducer(data, {"train": {}}, np.random.RandomState(2), 1, c["lr"], c["l"],
+                             c["r"], c["m"], c["s"], c["l1"], c["l2"], c["opt"], "traj", c["dec"],
+                             False, c["ext_reg"], False, c["alpha"], device=cuda_dev,
+                             graph_chunk=2, mfma_bf16=c["bf16"])
+    ind.learn(verbose=False)
+    got_c, got_p = np.array(ind.epoch_costs)[0], _params(ind)
+    ind._drop_engine()
+    want_c, want_p = _trajectory_oracle(c, data)
+    if c["bf16"]:
+        emu_c, emu_p = _trajectory_oracle(c, data, bf16=True)
+        check_bf16({"exact": (want_c, want_p), "emu": (emu_c, emu_p), "gpu": (got_c, got_p)},
+                   None, f"{shape} {option}")
+    else:
+        np.testing.assert_allclose(got_c, want_c, rtol=COST_RTOL, atol=COST_RTOL)
+        _assert_params_close(got_p, want_p, f"{shape} {option}")
