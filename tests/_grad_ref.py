@@ -1,5 +1,6 @@
 """Host references for one training step under every optimiser / regulariser option
-(tests/test_grad_ref.py pins them on the CPU, tests/test_gpu_options.py holds the device to them).
+(tests/test_grad_ref.py pins them on the CPU; tests/test_gpu_options.py holds the device to them at
+one rank, tests/test_gpu_dp_options.py the data-parallel forms at the same global batch).
 
 * a dataset whose batches hold every row class of the update (rows of the A and of the W table
   with exactly 1 record, 2-4, 5-16 and more than 16 records), and a "hot" variant with a row
@@ -14,6 +15,7 @@
 """
 import functools
 import math
+import sys
 
 import numpy as np
 import torch
@@ -63,10 +65,69 @@ CASES = [(sh, op) for sh in SHAPES
          for op in (tuple(OPTIONS) if sh in ALL_OPTIONS else ("O1", "O3"))]
 N_BATCHES = 3
 
+# Data-parallel cases (tests/test_gpu_dp_options.py).  A shape's batch is the GLOBAL batch L of
+# G ranks with l = L / G examples each, so the references of a case are those of the single-rank
+# case at l = L.  DP_SHAPES adds what SHAPES lacks: S4p, the forced split SP forward at L = 36
+# (three ranks of 12).
+DP_SHAPES = dict(SHAPES)
+DP_SHAPES["S4p"] = dict(dec="sp", mrsl=(8, 44, 5, 36), d=500, forms={"sp_forward": "split"},
+                        want={"sp_forward": "split"})
 
-def case_config(shape, option):
+
+def _dp_cases():
+    """(shape, option, G, dp_dense, priv_rows, partitioned): dp_dense / priv_rows None leave the
+    form to the plan; partitioned cases run the replicated update too (same forms) and compare
+    the two bitwise.  A regulariser (O1, O4) goes with the replicated update only."""
+    out = []
+
+    def add(shape, option, G, dense=None, priv=None, part=False):
+        out.append((shape, option, G, dense, priv, part))
+    for G in (2, 4):
+        for dense in ("records", "partials"):
+            for op in ("O1", "O3", "O4"):
+                add("S1", op, G, dense)
+    for dense in ("partials", "records"):
+        for priv in ("on", "off"):
+            for op in ("O0", "O3"):
+                add("S1", op, 2, dense, priv, True)
+    for G in (2, 5):                        # the scalar path; G = 5: 14 rows owned of L = 70
+        for dense in ("records", "partials"):
+            for op in ("O1", "O3"):
+                add("S3", op, G, dense, None, G == 5 and op == "O3")
+    for op in ("O1", "O3"):
+        add("S4p", op, 3, "partials")
+        add("B1", op, 2, part=op == "O3")
+        add("B2", op, 2)
+    for op in ("O1", "O3", "O4"):
+        add("H1", op, 4, part=op == "O3")
+    for op in ("O1", "O3"):
+        add("B4", op, 2)
+        add("B5", op, 2, part=op == "O3")   # L = 40: Lp = 64 has 24 padding examples
+    add("B6", "O3", 2)                      # m > 128
+    add("H3", "O3", 2)
+    for shape in ("X1", "X2"):
+        add(shape, "O3", 2, part=True)
+        add(shape, "O1", 2)
+    return out
+
+
+DP_CASES = _dp_cases()
+
+
+def dp_case_id(case):
+    shape, option, G, dense, priv, part = case
+    return (f"{shape}-{option}-G{G}" + (f"-{dense}" if dense else "") +
+            (f"-priv_{priv}" if priv else "") + ("-part" if part else ""))
+
+
+def dp_case_config(shape, option):
+    """The global-batch config of a data-parallel case (l is the global batch L)."""
+    return case_config(shape, option, DP_SHAPES)
+
+
+def case_config(shape, option, shapes=None):
     """Everything one (shape, option) case needs, as a dict."""
-    c = dict(SHAPES[shape])
+    c = dict((shapes or SHAPES)[shape])
     c.update(OPTIONS[option])
     c["m"], c["r"], c["s"], c["l"] = c.pop("mrsl")
     c["n"] = 20000 if (c["l"], c["s"]) == (100, 20) else 4000
@@ -286,3 +347,82 @@ def emulate_opt_update(p, acc, g, lr, opt):
         return (p - step).astype(np.float32), a
     # SGD: one rounding of p - lr g (an fma)
     return (p.astype(np.float64) - np.float64(lr) * g.astype(np.float64)).astype(np.float32), acc
+
+
+# --------------------------------------------------------------------------------------------
+# the assertions of one step (tests/test_gpu_options.py, tests/test_gpu_dp_options.py; on the
+# CPU tests/test_grad_ref.py feeds them planted states)
+# --------------------------------------------------------------------------------------------
+COST_RTOL = 2e-5            # tests/test_gpu_train.py
+BF16_EXACT_FACTOR, BF16_EMU_FACTOR = 1.25, 0.25     # tests/test_gpu_fullscale.py
+G = sys.modules[__name__]   # the names below are written as the tests write them
+
+
+def _check_step(c, b, cost, p1, acc, tag, bad):
+    """The assertions of one batch; failures are appended to `bad` (so every ratio of the case
+    is printed before the test fails)."""
+    ref = G.references(c, b)
+    p0 = G.generic_params(c)
+    lr = c["lr"]
+    want = ref["cost64"]
+    if c["bf16"]:
+        dc = abs(ref["cost_emu"] - want)
+        ok = (abs(cost - want) <= BF16_EXACT_FACTOR * dc + COST_RTOL * abs(want) and
+              abs(cost - ref["cost_emu"]) <= BF16_EMU_FACTOR * dc + COST_RTOL * abs(want))
+    else:
+        ok = abs(cost - want) <= COST_RTOL * max(1.0, abs(want))
+    print(f"COST {tag} b{b} gpu {cost:.9g} oracle {want:.9g} rel {abs(cost - want) / abs(want):.2e}")
+    if not ok:
+        bad.append(f"b{b} cost {cost!r} oracle {want!r}")
+    for k, g64 in ref["g64"].items():
+        t = G.tolerance(ref["rho32"][k])
+        emu = ref["rho_emu"][k] if c["bf16"] else 0.0
+        tol_exact = BF16_EXACT_FACTOR * emu + t
+        a0 = p0[k].astype(np.float64)
+        a1 = p1[k].astype(np.float64)
+        rm = G.row_max(g64)
+        # rows with an exactly zero gradient: never written
+        zero = rm == 0.0
+        if not np.array_equal(p1[k][zero], p0[k][zero]):
+            bad.append(f"b{b} {k}: an untouched row changed")
+        if c["opt"] == "adagrad":
+            ak = acc[k].astype(np.float64)
+            if np.any(ak[zero] != 0.0):
+                bad.append(f"b{b} {k}: accumulator of an untouched row is not zero")
+            g = G.extract_adagrad(a0, a1, ak, g64, tol_exact)
+            # the step's size from the accumulator alone (its sign is in g, checked by rho)
+            step = lr * np.sqrt(ak) / (np.sqrt(ak) + 1e-6)
+            off = np.abs(np.abs(a0 - a1) - step)
+            if not np.all(off <= 8 * 2.0 ** -24 * (np.abs(a0) + lr)):
+                bad.append(f"b{b} {k}: p1 is not the AdaGrad step of sqrt(acc): {off.max():.3e}")
+            slack = 0.0
+        else:
+            g = (a0 - a1) / lr
+            slack = 2.0 ** -23 * np.abs(a1) / lr      # the one rounding of p1
+        r_gpu = _rho_slack(g, g64, slack)
+        ratio = r_gpu / max(ref["rho32"][k], G.FLOOR)
+        line = (f"RATIO {tag} b{b} {k:2s} rho_gpu {r_gpu:.3e} rho_host32 {ref['rho32'][k]:.3e} "
+                f"ratio {ratio:.3f}")
+        if c["bf16"]:
+            if c["opt"] == "adagrad":       # the sign rule against this reference's own tolerance
+                g = G.extract_adagrad(a0, a1, ak, ref["g_emu"][k], BF16_EMU_FACTOR * emu + t)
+            r_emu = _rho_slack(g, ref["g_emu"][k], slack)
+            line += f" rho_emu {emu:.3e} rho_gpu_emu {r_emu:.3e}"
+            if not r_emu <= BF16_EMU_FACTOR * emu + t:
+                bad.append(f"b{b} {k}: rho(gpu, emu) {r_emu:.3e} > 0.25 * {emu:.3e} + {t:.3e}")
+        print(line)
+        if not r_gpu <= tol_exact:
+            bad.append(f"b{b} {k}: rho(gpu, f64) {r_gpu:.3e} > {tol_exact:.3e} "
+                       f"(host32 {ref['rho32'][k]:.3e}, ratio {ratio:.2f})")
+
+
+def _rho_slack(x, g, slack):
+    """rho(x, g) with a per-element allowance `slack` taken off |x - g| first (SGD: the rounding
+    of p1, which is not the gradient's error)."""
+    if np.isscalar(slack):
+        return G.rho(x, g)
+    err = np.maximum(np.abs(x - g) - slack, 0.0)
+    zero = G.row_max(g) == 0.0
+    if np.any(np.asarray(x)[zero] != 0.0):
+        return float("inf")
+    return G.rho(g + err, g)

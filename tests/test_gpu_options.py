@@ -33,11 +33,9 @@ import numpy as np
 import pytest
 
 import _grad_ref as G
+from _grad_ref import COST_RTOL, _check_step     # the assertions of one step live there
 
 pytestmark = pytest.mark.gpu
-
-COST_RTOL = 2e-5            # tests/test_gpu_train.py
-BF16_EXACT_FACTOR, BF16_EMU_FACTOR = 1.25, 0.25     # tests/test_gpu_fullscale.py
 
 
 def _expected_forms(c):
@@ -93,76 +91,6 @@ def _one_step_states(c, dev, forms=None, per_call=False):
     forms_used = eng.kernel_forms_in_use()
     ind._drop_engine()
     return out, forms_used
-
-
-def _check_step(c, b, cost, p1, acc, tag, bad):
-    """The assertions of one batch; failures are appended to `bad` (so every ratio of the case
-    is printed before the test fails)."""
-    ref = G.references(c, b)
-    p0 = G.generic_params(c)
-    lr = c["lr"]
-    want = ref["cost64"]
-    if c["bf16"]:
-        dc = abs(ref["cost_emu"] - want)
-        ok = (abs(cost - want) <= BF16_EXACT_FACTOR * dc + COST_RTOL * abs(want) and
-              abs(cost - ref["cost_emu"]) <= BF16_EMU_FACTOR * dc + COST_RTOL * abs(want))
-    else:
-        ok = abs(cost - want) <= COST_RTOL * max(1.0, abs(want))
-    print(f"COST {tag} b{b} gpu {cost:.9g} oracle {want:.9g} rel {abs(cost - want) / abs(want):.2e}")
-    if not ok:
-        bad.append(f"b{b} cost {cost!r} oracle {want!r}")
-    for k, g64 in ref["g64"].items():
-        t = G.tolerance(ref["rho32"][k])
-        emu = ref["rho_emu"][k] if c["bf16"] else 0.0
-        tol_exact = BF16_EXACT_FACTOR * emu + t
-        a0 = p0[k].astype(np.float64)
-        a1 = p1[k].astype(np.float64)
-        rm = G.row_max(g64)
-        # rows with an exactly zero gradient: never written
-        zero = rm == 0.0
-        if not np.array_equal(p1[k][zero], p0[k][zero]):
-            bad.append(f"b{b} {k}: an untouched row changed")
-        if c["opt"] == "adagrad":
-            ak = acc[k].astype(np.float64)
-            if np.any(ak[zero] != 0.0):
-                bad.append(f"b{b} {k}: accumulator of an untouched row is not zero")
-            g = G.extract_adagrad(a0, a1, ak, g64, tol_exact)
-            # the step's size from the accumulator alone (its sign is in g, checked by rho)
-            step = lr * np.sqrt(ak) / (np.sqrt(ak) + 1e-6)
-            off = np.abs(np.abs(a0 - a1) - step)
-            if not np.all(off <= 8 * 2.0 ** -24 * (np.abs(a0) + lr)):
-                bad.append(f"b{b} {k}: p1 is not the AdaGrad step of sqrt(acc): {off.max():.3e}")
-            slack = 0.0
-        else:
-            g = (a0 - a1) / lr
-            slack = 2.0 ** -23 * np.abs(a1) / lr      # the one rounding of p1
-        r_gpu = _rho_slack(g, g64, slack)
-        ratio = r_gpu / max(ref["rho32"][k], G.FLOOR)
-        line = (f"RATIO {tag} b{b} {k:2s} rho_gpu {r_gpu:.3e} rho_host32 {ref['rho32'][k]:.3e} "
-                f"ratio {ratio:.3f}")
-        if c["bf16"]:
-            if c["opt"] == "adagrad":       # the sign rule against this reference's own tolerance
-                g = G.extract_adagrad(a0, a1, ak, ref["g_emu"][k], BF16_EMU_FACTOR * emu + t)
-            r_emu = _rho_slack(g, ref["g_emu"][k], slack)
-            line += f" rho_emu {emu:.3e} rho_gpu_emu {r_emu:.3e}"
-            if not r_emu <= BF16_EMU_FACTOR * emu + t:
-                bad.append(f"b{b} {k}: rho(gpu, emu) {r_emu:.3e} > 0.25 * {emu:.3e} + {t:.3e}")
-        print(line)
-        if not r_gpu <= tol_exact:
-            bad.append(f"b{b} {k}: rho(gpu, f64) {r_gpu:.3e} > {tol_exact:.3e} "
-                       f"(host32 {ref['rho32'][k]:.3e}, ratio {ratio:.2f})")
-
-
-def _rho_slack(x, g, slack):
-    """rho(x, g) with a per-element allowance `slack` taken off |x - g| first (SGD: the rounding
-    of p1, which is not the gradient's error)."""
-    if np.isscalar(slack):
-        return G.rho(x, g)
-    err = np.maximum(np.abs(x - g) - slack, 0.0)
-    zero = G.row_max(g) == 0.0
-    if np.any(np.asarray(x)[zero] != 0.0):
-        return float("inf")
-    return G.rho(g + err, g)
 
 
 VARIANTS = [(s, o, None, False) for s, o in G.CASES] + [

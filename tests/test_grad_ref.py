@@ -1,7 +1,9 @@
 """The host references of tests/_grad_ref.py, on the CPU: the two float64 derivations of one
 step's gradients agree under every option, the extraction of a gradient from the state an
 AdaGrad step leaves round-trips, and the tolerances of tests/test_gpu_options.py reject each of
-a list of planted errors using the host references alone."""
+a list of planted errors using the host references alone; the checker the GPU tests share
+(_grad_ref._check_step) reports a data-parallel plan's dense gradients taken over l instead of
+L, under both optimisers, and nothing for the unscaled state."""
 import numpy as np
 import pytest
 import scipy.sparse as sp
@@ -161,3 +163,69 @@ def test_tolerances_reject_planted_errors(shape):
                              lambda1=c["l1"], lambda2=c["l2"], adjust=adjust,
                              ext_reg=c["ext_reg"])
     assert "W" in _caught(ref, res.grads)
+
+
+# --------------------------------------------------------------------------------------------
+# the data-parallel cases (tests/test_gpu_dp_options.py)
+# --------------------------------------------------------------------------------------------
+def test_dp_datasets_hold_every_row_class():
+    """Every batch of every data-parallel case's dataset holds every row class of both tables
+    (options_dataset asserts it; the new L = 36 set is looked at here batch by batch), the hot
+    sets a row of at least 256 records; the global batch divides into the ranks, and no
+    partitioned case carries a regulariser (plan_resolve refuses the pair)."""
+    for case in G.DP_CASES:
+        shape, option, ranks, dense, priv, part = case
+        c = G.dp_case_config(shape, option)
+        data, n1, n2 = G.case_dataset(c)
+        assert c["l"] % ranks == 0 and data.split["train"].args1.shape[0] == G.N_BATCHES * c["l"]
+        assert not (part and (c["l1"] != 0.0 or c["l2"] != 0.0)), case
+        assert dense is None or c["dec"] == "sp", case
+        if c["hot"]:
+            for b in range(G.N_BATCHES):
+                assert G.batch_row_classes(data, n1, n2, c["l"], b)[0].max() >= 256
+    assert len({G.dp_case_id(case) for case in G.DP_CASES}) == len(G.DP_CASES)
+    c = G.dp_case_config("S4p", "O1")
+    assert (c["l"], c["n"], c["d"]) == (36, 4000, 500)
+    data, n1, n2 = G.case_dataset(c)
+    for b in range(G.N_BATCHES):
+        ca, cw = G.batch_row_classes(data, n1, n2, c["l"], b)
+        assert min(G._class_counts(ca)) > 0 and min(G._class_counts(cw)) > 0, b
+    assert G.SHAPES.keys() == G.DP_SHAPES.keys() - {"S4p"}
+    assert all(G.DP_SHAPES[k] is G.SHAPES[k] for k in G.SHAPES)
+
+
+def _state_of(c, b, scale):
+    """The state a device that computed the float32 host gradient -- tensor k's times
+    scale.get(k, 1) -- would leave after batch b: (cost, p1, acc), by opt_update in float32."""
+    ref = G.references(c, b)
+    p0 = G.generic_params(c)
+    p1, acc = {}, {}
+    for k, g in ref["g32"].items():
+        g = (g * scale.get(k, 1.0)).astype(np.float32)
+        p1[k], a = G.emulate_opt_update(p0[k], np.zeros_like(p0[k]), g, c["lr"], c["opt"])
+        if c["opt"] == "adagrad":
+            acc[k] = a
+    return ref["cost32"], p1, acc
+
+
+def _reported(bad):
+    """The tensors (or "cost") _check_step's failure lines name."""
+    return sorted({line.split()[1].rstrip(":") for line in bad})
+
+
+@pytest.mark.parametrize("option", ["O3", "O0"])
+def test_checker_reports_dense_gradients_over_l_instead_of_L(option):
+    """What the data-parallel tests exist to catch: the dense tensors' gradient (C1, C2, Wb) of
+    a 2-rank plan normalised by l instead of L, i.e. scaled by l / L = 1 / 2.  AdaGrad's step is
+    invariant to such a factor up to its epsilon (lr g / (|g| + 1e-6) from a zero accumulator), so
+    the parameters hardly tell; _check_step reads |g| from sqrt(acc) and reports exactly those
+    tensors, as it does under SGD from p0 - p1.  The unscaled float32 host state passes."""
+    c = G.case_config("S1", option)
+    assert c["opt"] == ("sgd" if option == "O3" else "adagrad")
+    dense = {"C1": 0.5, "C2": 0.5, "Wb": 0.5}
+    for b in range(G.N_BATCHES):
+        bad = []
+        G._check_step(c, b, *_state_of(c, b, {}), f"host32-{option}", bad)
+        assert bad == []
+        G._check_step(c, b, *_state_of(c, b, dense), f"halved-{option}", bad)
+        assert _reported(bad) == sorted(dense), bad
