@@ -647,6 +647,9 @@ struct rae_plan : PlanSpec {
     int peers_mask = 0;
     char* ws = nullptr;
     unsigned long long* stamps_fwd = nullptr;
+#ifdef RAE_WSTAMPS
+    unsigned long long* stamps_wave = nullptr;
+#endif
     unsigned long long* stamps_upd = nullptr;
     hipEvent_t t_start = nullptr, t_stop = nullptr;   // armed by rae_time_next for ONE call
 };
@@ -912,6 +915,9 @@ static int launch_forward(rae_plan* p, const int64_t* cursor, int64_t off, hipSt
     a.cursor = cursor;
     a.step_offset = off;
     a.stamps = p->stamps_fwd;
+#ifdef RAE_WSTAMPS
+    a.wstamps = p->stamps_wave;
+#endif
     const bool p2p = p2p_on(p);
     if (p2p) {
         if (!p->peers_set) return fail(RAE_E_STATE, "peer buffers not set (rae_set_peer)");
@@ -1345,6 +1351,16 @@ extern "C" int rae_debug_grid(rae_plan* p, int* out) {
     out[0] = p->grid_fwd; out[1] = p->grid_update; out[2] = 0; out[3] = 0;
     return RAE_OK;
 }
+#ifdef RAE_WSTAMPS
+// the fast SP forward's per-wave stamps (tools/c_stream_stamps.py): a buffer of their own, 8 u64
+// per wave = 64 per forward block, so a library built with them stays safe under the tools that
+// pass rae_debug_stamps' 16 u64 per block (null: no wave stamps are written)
+extern "C" int rae_debug_wave_stamps(rae_plan* p, unsigned long long* buf) {
+    if (!p) return fail(RAE_E_INVALID, "null plan");
+    p->stamps_wave = buf;
+    return RAE_OK;
+}
+#endif
 #endif
 
 // the device error word, bit by bit (rae.h): a peer-to-peer wait timeout is a state error (a

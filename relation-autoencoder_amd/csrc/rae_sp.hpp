@@ -29,9 +29,6 @@ namespace rae {
 
 #define RAE_FNW (RAE_FBT / RAE_WAVE)     // waves per forward workgroup
 #define RAE_NG (RAE_FBT / 16)            // 16-lane groups per forward workgroup
-#ifndef RAE_CEARLY
-#define RAE_CEARLY 0   // measured: C loads first delay the id chain (vmcnt is in order)
-#endif
 
 // ---- compile-time or runtime shapes ------------------------------------------------------
 struct DynDims {
@@ -207,12 +204,18 @@ struct CCacheW {
     // branch-free: out-of-range rows/columns load a clamped (valid) element; their
     // contributions are multiplied by zero-padded P / zeroed dw
     __device__ __forceinline__ void load(const StepArgs& a, const D& Dm, int r0, int c0) {
+        load_rows<0, RA>(a, Dm, r0, c0);
+    }
+    // row groups ra = RA_B .. RA_E-1 only (the fast path issues C in two tranches)
+    template <int RA_B, int RA_E>
+    __device__ __forceinline__ void load_rows(const StepArgs& a, const D& Dm, int r0, int c0) {
+        static_assert(0 <= RA_B && RA_B <= RA_E && RA_E <= RA, "row-group range");
         const VT* C1v = reinterpret_cast<const VT*>(a.C1);
         const VT* C2v = reinterpret_cast<const VT*>(a.C2);
         const int mv = Dm.m / VW;
         const int gid = threadIdx.x >> 4, q = threadIdx.x & 15;
 #pragma unroll
-        for (int ra = 0; ra < RA; ++ra) {
+        for (int ra = RA_B; ra < RA_E; ++ra) {
 #if RAE_KO_C     // diagnostic knockout (wrong results): every lane reads row 0 (L1-hot C)
             const int i = 0;
 #else
@@ -828,11 +831,25 @@ __device__ __forceinline__ void sp_coef_rows_regs(const StepArgs& a, const D& Dm
 #ifndef RAE_FWD_PFLAG
 #define RAE_FWD_PFLAG 1      // fast path: P published by an LDS flag, not a block barrier
 #endif
-#ifndef RAE_FWD_CWAIT
-#define RAE_FWD_CWAIT 1      // fast path: C loads last on every wave, C.P in load order
+// fast path: the row groups of C1 / C2 (of CCacheW::RA per thread) that waves 4-7 issue at kernel
+// entry; the rest follows their A-row DMAs.  7 = their whole share (profiles/r07_ab.txt has the
+// other splits)
+#ifndef RAE_FWD_CE47
+#define RAE_FWD_CE47 7
 #endif
-#ifndef RAE_FWD_CEARLY47
-#define RAE_FWD_CEARLY47 0   // fast path: waves 4-7 issue their C share at kernel start
+#define RAE_WAIT_VM0 0x0F70  // s_waitcnt vmcnt(0) alone on gfx9: expcnt 7, lgkmcnt 15 = no wait
+// per-wave stamps of the fast path (tools/c_stream_stamps.py; 8 u64 per wave into a buffer of
+// their own, StepArgs::wstamps, set by rae_debug_wave_stamps): taken into registers where the wave
+// waits anyway and stored at the end of the kernel
+#if defined(RAE_WSTAMPS) && !defined(RAE_STAMPS)
+#error "RAE_WSTAMPS extends RAE_STAMPS (a diagnostic build)"
+#endif
+#ifdef RAE_WSTAMPS
+#define RAE_WSTAMP_T(k) (wst[k] = __builtin_amdgcn_s_memrealtime())
+#define RAE_WSTAMP_WAIT(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
+#else
+#define RAE_WSTAMP_T(k) do { } while (0)
+#define RAE_WSTAMP_WAIT(n) do { } while (0)
 #endif
 template <bool V4, class D>
 __device__ void sp_example(const StepArgs& a, int64_t g, int bl, char* smem) {
@@ -853,14 +870,7 @@ __device__ void sp_example(const StepArgs& a, int64_t g, int bl, char* smem) {
     if (a.stamps && threadIdx.x == 0) a.stamps[(size_t)blockIdx.x * 16 + 14] = __builtin_amdgcn_s_memtime();
 #endif
     CCache<V4, D> cc_;
-#if RAE_CEARLY
-    // the decoder matrices do not depend on the batch: their loads go out first and land
-    // while the id -> feature -> W-row chain runs
-    if (CCache<V4, D>::FITS) cc_.load(a, Dm, 0, 0);
-    constexpr bool kLoadC = false;
-#else
     constexpr bool kLoadC = CCache<V4, D>::FITS;
-#endif
     load_desc(a, Dm, g, bl, S);
     __syncthreads();
     RAE_STAMP(a, 1);
@@ -906,9 +916,16 @@ __device__ void sp_example(const StepArgs& a, int64_t g, int bl, char* smem) {
 // inline asm: the compiler's wait-count pass treats every LDS access behind an LDS-DMA it can
 // see as a possible alias and puts a vmcnt(0) -- every outstanding load -- in front of it, which
 // in the fast path serialised the W-row partial sums, the P hand-off and C.P behind the whole
-// 160 KB of decoder-matrix loads.  Issued before those loads, an LDS-DMA the pass cannot see
-// only ever makes its counted waits wait for more (vmcnt retires in issue order); the rows are
-// read after dma_visible_barrier (vmcnt(0) + barrier).
+// 160 KB of decoder-matrix loads.  Waves 4-7 issue: early C (row groups ra < E47) -> A-row DMAs
+// -> Ab -> rest of C.  vmcnt retires in issue order and a counted wait vmcnt(n) returns once at
+// most n of ALL the wave's outstanding ops remain, so the DMAs the pass cannot see only ever
+// make its waits wait for more, wherever they stand in the order: the pass's vmcnt(n) for a C
+// register assumes n loads issued behind it; with k unseen DMAs also behind it (k = all of them
+// for an early register, 0 for a late one) n + k are, and "at most n remain" then means that
+// register AND the k ops next in line have landed.  So an early register's product waits for
+// up to 10-11 ops more than it needs -- later early C or A rows, issued ~2 us before C.P
+// starts -- and never for fewer; a late register's wait is exact.  The rows are read after
+// dma_visible_barrier (vmcnt(0) + barrier).
 // M0 is a reserved register the compiler cannot take as a clobber: the asm saves it into a
 // scratch SGPR and restores it behind the load (the instruction reads M0 at issue), so any M0
 // value the compiler keeps live across the block -- e.g. for its own global_load_lds -- is
@@ -977,10 +994,10 @@ __device__ __forceinline__ void fast_softmax(const StepArgs& a, ExampleSmem& S, 
 // ---- the SP example path for compile-time shapes (BASELINE configs) ---------------------
 // Same arithmetic as sp_example, re-timed for a 100-example step where the kernel is a
 // dependent chain: waves 0-3 run the critical chain (ids -> feature ids -> W rows -> S ->
-// softmax) while waves 4-7 issue the A-row LDS-DMA and the Ab loads, and every wave
-// then issues its share of the decoder-matrix loads.  No barrier drains vmcnt until the
-// decoder matrices are needed (lds_barrier), so the ~200 KB of bulk loads per CU overlap
-// the chain instead of sitting in front of it.  Softmax and the score coefficients use
+// softmax) and issue their share of the decoder-matrix loads behind their W rows, while waves
+// 4-7 issue theirs at kernel entry, under the descriptor round trip, and then the A-row LDS-DMA
+// and the Ab loads.  No barrier drains vmcnt until the decoder matrices are needed
+// (lds_barrier), so the ~200 KB of bulk loads per CU overlap the chain.  Softmax and the score coefficients use
 // hardware exp/log/rcp; the coefficient work is spread over 2s lanes.
 template <class D> struct FastSP { static constexpr int VM = 4; static constexpr bool ok = false; };
 template <int M, int R, int S> struct FastSP<FixDims<M, R, S>> {
@@ -1014,175 +1031,223 @@ __device__ void sp_example_fast(const StepArgs& a, int64_t g, int bl, char* smem
 #ifdef RAE_STAMPS
     if (a.stamps && threadIdx.x == 0) a.stamps[(size_t)blockIdx.x * 16 + 14] = __builtin_amdgcn_s_memtime();
 #endif
-    CCF cc_;
-#if RAE_FWD_CWAIT && RAE_FWD_CEARLY47
-    // waves 4-7 have no load on the chain: their half of C goes out at once (the other half
-    // follows the W rows of waves 0-3), so C's ingest starts ~1 us earlier
-    if (w >= 4) cc_.load(a, Dm, 0, 0);
+#ifdef RAE_WSTAMPS
+    unsigned long long wst[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #endif
-    // the example's descriptor (rae_index.hpp build_batch_desc): feature count, CSR start,
-    // entity ids and feature ids in one coalesced read
-    {
+    RAE_WSTAMP_T(0);
+    CCF cc_;
+    // Up to C.P the two wave roles run DISJOINT code, the two sides of one wave-uniform branch,
+    // with the same barriers on both sides (s_barrier counts arrivals, whatever the PC):
+    //   waves 4-7: early C (row groups ra < E47, the wave's first vector-memory ops) | A-row
+    //              DMAs | Ab | rest of C | wait for P
+    //   waves 0-3: descriptor | W rows, bias | all of C | partial sums | wave 0: softmax, P
+    // Nothing on waves 4-7 waits for a load before C.P: their barriers drain lgkmcnt only.
+    // Why disjoint code and not role tests in common code: the wait-count pass follows control
+    // flow, not wave roles.  A load that any path into a merge leaves pending is pending behind
+    // the merge for every wave, counted with the fewest loads any path issues behind it.  With
+    // the early loads ahead of common code, (a) the descriptor word, the feature values and wave
+    // 0's bias loads -- waited for inside per-lane branches a wave may skip -- counted as pending
+    // with only Ab behind them, so the next write of their registers waited with vmcnt(2), all
+    // but two of a chain wave's C loads, in front of the softmax; (b) waves 0-3's C loads write
+    // the registers waves 4-7 loaded early, a write-after-write the pass covered by waiting for
+    // the W rows in the middle of waves 0-3's C issue.  Both seen in the disassembly of the
+    // role-test form; neither exists when no path runs both roles' loads.
+    // A rule of thumb, not a measured threshold: only two shapes reach this code, C3 (160 KB of
+    // C1 + C2, tranche -0.5 us) and C2 (24 KB, tranche +0.09 us of forward: 5.37 -> 5.47 us,
+    // measured on the form before this rule existed; with the rule C2 equals the parent,
+    // profiles/r07_ab.txt).  The cut is put at the CU's 32 KB L1, which lies between them: what
+    // fits it streams in behind the gathers in ~0.2 us anyway.  A shape in between needs its own
+    // measurement.
+    constexpr bool kEarly = 2 * r * m * (int)sizeof(float) > 32 * 1024;
+    constexpr int E47 = !kEarly ? 0 : RAE_FWD_CE47 < CCF::RA ? RAE_FWD_CE47 : CCF::RA;
+    constexpr int NI = mp / RAE_WAVE;
+    static_assert(CCF::FITS && CCF::CC <= 2, "fast path keeps C1/C2 in registers");
+    static_assert(r / 4 <= RAE_WAVE, "one DMA instruction per A row");
+    float abv = 0.f;
+    bool general;
+    if (w >= 4) {
+        // At once: the CU's memory queue is in issue order, so the descriptor read of waves 0-1
+        // (issued behind a scalar address chain) lands later than with no tranche in front of
+        // it, but C lands earlier by more (profiles/r07_c3_cstream_stamps.txt); holding the
+        // tranche back by s_sleep 4 / 8 / 16 measured slower each step of the way, and so did
+        // the smaller tranches (profiles/r07_ab.txt).
+        cc_.template load_rows<0, E47>(a, Dm, 0, 0);
+        RAE_WSTAMP_T(1);
+        lds_barrier();                       // the descriptor is in LDS
+        const int nf = S.sint[1];
+        general = nf > a.dcap || nf > NSL * KF;
+        // A general row (rare) skips only what the pass cannot see -- the barriers waves 0-3 skip
+        // too, and the A-row DMAs, which must not race the general path's own staging.  Ab and
+        // the rest of C are issued either way: were they under the branch, the path without
+        // them would reach the block C.P starts from with the early registers counted as having
+        // few loads behind them, and C.P's first products would wait for nearly all of C (seen
+        // in the disassembly: vmcnt(15) in front of the first product at E47 = 4).
+        if (!general) {
+            if (a.values) lds_barrier();     // waves 0-3 stage the feature values
+            lds_barrier();                   // every W-row load is issued
+            // A rows by LDS-DMA, one row per wave instruction (r / 4 = 50 lanes x 16 B), rows
+            // w-4, w, w+4, ...: a fixed unrolled count, as inline asm (dma_row16)
+            constexpr int RPW4 = (NR + 3) / 4;
+            const int ln = lane < r / 4 ? lane : 0;
+#pragma unroll
+            for (int k = 0; k < RPW4; ++k) {
+                const int rho = (w - 4) + 4 * k;
+                if (rho < NR && lane < r / 4) {
+                    const int j = rho == 0 ? 0 : rho + 1;            // SP: e2's row is not read
+                    const float* src = a.A + (int64_t)(RAE_KO_A ? 0 : S.sids[j]) * r + (int64_t)ln * 4;
+                    dma_row16(src, lds_addr(arows + rho * r4));
+                }
+            }
+        }
+        if (tid - 256 < NJ) abv = a.Ab[S.sids[tid - 256]];
+        asm volatile("" ::: "memory");
+        cc_.template load_rows<E47, CCF::RA>(a, Dm, 0, 0);
+        asm volatile("" ::: "memory");       // pins them here: a general row has no use for C,
+                                             // and the compiler had sunk them under !general
+        RAE_WSTAMP_T(2);
+        if (!general) {
+#ifdef RAE_WSTAMPS
+            // these waves only poll the P flag from here, so the two waits cost the chain
+            // nothing: until only the late C loads are outstanding (the A-row DMAs, Ab and the
+            // early C have landed), then until the wave's last C register has landed
+            RAE_WSTAMP_WAIT((CCF::RA - E47) * CCF::CC * 2);
+            RAE_WSTAMP_T(3);
+            RAE_WSTAMP_WAIT(0);
+            RAE_WSTAMP_T(4);
+#endif
+            // P / Z / H ready: an LDS flag instead of a block barrier, so the waves that run the
+            // chain do not wait for these waves, still issuing (and back-pressured on) bulk loads
+            if (RAE_FWD_PFLAG) {
+                while (__hip_atomic_load(&S.sint[5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0)
+                    __builtin_amdgcn_s_sleep(1);
+            } else {
+                lds_barrier();
+            }
+        }
+    } else {
+        // the example's descriptor (rae_index.hpp build_batch_desc): feature count, CSR start,
+        // entity ids and the feature ids this path can use (a row with more than NSL*KF leaves
+        // for the general path, which reads its own) in one coalesced read
+        constexpr int DN = 2 + NJ + NSL * KF;
+        static_assert(DN <= 4 * RAE_WAVE, "the descriptor read is waves 0-3's");
         const int32_t* dsc = a.desc + ((g % a.index_window) * a.dnx + a.d0 + bl) * (int64_t)a.dstride;
-        if (tid < a.dstride) {
+        if (tid < DN && tid < a.dstride) {
             const int v = dsc[tid];
             if (tid == 0) S.sint[1] = v;                          // nf
             else if (tid == 1) S.sint[0] = v;                     // p0
             else if (tid < 2 + NJ) S.sids[tid - 2] = v;
-            else if (tid - 2 - NJ < 256) {
+            else {
                 S.sfidx[tid - 2 - NJ] = v;
                 S.sfval[tid - 2 - NJ] = 1.f;
             }
         }
-    }
-    constexpr int NI = mp / RAE_WAVE;
-    float wbk[NI];                           // wave 0: the bias entries it reduces
+        if (tid == 0) {
+            S.sint[4] = 0;                   // arrival counter of the W-row waves
+            S.sint[5] = 0;                   // P ready (RAE_FWD_PFLAG)
+        }
+        // The descriptor word is waited for inside per-lane branches, so a path exists on which
+        // the pass counts it pending -- on the general row's, with no load behind it, and that
+        // path and C.P leave the same block: the first write of its register in C.P then waited
+        // with vmcnt(0), for all of C.  A wait the pass can see (a builtin, not asm) ends that
+        // here, where waves 0-1 wait for the descriptor anyway and nothing else is in flight.
+        __builtin_amdgcn_s_waitcnt(RAE_WAIT_VM0);
+        RAE_WSTAMP_T(1);
+        lds_barrier();
+        RAE_STAMP(a, 1);
+        const int p0 = S.sint[0], nf = S.sint[1];
+        // rows with more features than the W-row registers hold (NSL*KF = 30 at C3; the
+        // synthetic C3 rows have 9..39, P(nf > 30) ~ 1e-6) or than the descriptor holds take the
+        // general path: then the decoder-matrix loads are the LAST vector-memory ops of these
+        // waves, so C.P waits for each C load by a counted vmcnt and runs while the rest lands
+        general = nf > a.dcap || nf > NSL * KF;
+        if (!general) {
+            if (a.values) {                  // non-binary features: their values
+                if (tid < nf) S.sfval[tid] = a.values[p0 + tid];
+                __builtin_amdgcn_s_waitcnt(RAE_WAIT_VM0);   // as above: nothing else is in flight
+                lds_barrier();
+            }
+            RAE_STAMP(a, 10);
+            // Issue order W rows -> decoder matrices: vmcnt and the CU's memory queue are in
+            // issue order, so the 5 KB of W rows the chain waits on go out first.
+            // W rows: slot = feature lane group, c = float4 column.
+            const MT* Wm = reinterpret_cast<const MT*>(a.W);
+            const int slot = tid / MV, c = tid - slot * MV;
+            MT wv[KF];
+            float fv[KF];
 #pragma unroll
-    for (int i = 0; i < NI; ++i) {
-        const int k = lane + RAE_WAVE * i;
-        wbk[i] = (w == 0 && k < m) ? a.Wb[k] : 0.f;
-    }
-    if (tid == 0) {
-        S.sint[4] = 0;                       // arrival counter of the W-row waves
-        S.sint[5] = 0;                       // P ready (RAE_FWD_PFLAG)
-    }
-    lds_barrier();
-    RAE_STAMP(a, 1);
-    const int p0 = S.sint[0], nf = S.sint[1];
-#if RAE_FWD_CWAIT
-    // rows with more features than the W-row registers hold (NSL*KF = 30 at C3; the synthetic
-    // C3 rows have 9..39, P(nf > 30) ~ 1e-6) take the general path: then the decoder-matrix
-    // loads are the LAST vector-memory ops of every wave, so C.P waits for each C load by a
-    // counted vmcnt and runs while the rest of C lands
-    if (nf > a.dcap || nf > NSL * KF) {
-#else
-    if (nf > a.dcap) {                       // longer than the descriptor holds: general path
+            for (int k = 0; k < KF; ++k) {
+                const int f = slot + NSL * k;
+                const bool ok = slot < NSL && f < nf;
+                const int fi = RAE_KO_W ? 0 : S.sfidx[f < 256 ? f : 255];   // knockout: row 0
+                wv[k] = Wm[(int64_t)(ok ? fi : 0) * MV + c];
+                fv[k] = ok ? S.sfval[f < 256 ? f : 255] : 0.f;
+            }
+            // wave 0: the bias entries it reduces, behind its W rows (on this path only, with
+            // all of C issued behind them: no wait before the softmax covers more than they do)
+            float wbk[NI];
+#pragma unroll
+            for (int i = 0; i < NI; ++i) {
+                const int k = lane + RAE_WAVE * i;
+                wbk[i] = (w == 0 && k < m) ? a.Wb[k] : 0.f;
+            }
+            lds_barrier();                   // every W-row load is issued
+            RAE_STAMP(a, 11);
+            asm volatile("" ::: "memory");
+            cc_.template load_rows<0, CCF::RA>(a, Dm, 0, 0);
+            RAE_WSTAMP_T(2);
+            {
+                MT acc;
+                vzero(acc);
+#pragma unroll
+                for (int k = 0; k < KF; ++k) vfma(acc, fv[k], wv[k]);
+                if (slot < NSL) reinterpret_cast<MT*>(S.spart)[slot * MV + c] = acc;
+            }
+            RAE_WSTAMP_T(3);                 // the W rows have landed
+            RAE_STAMP(a, 12);
+            // S = X.W + Wb and the softmax run in wave 0 as soon as waves 0-3 have their partial
+            // sums in LDS (LDS arrival counter) -- not behind a block barrier, which would also
+            // wait for waves 4-7, still issuing (and back-pressured on) the bulk loads.
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            if (lane == 0) atomicAdd(&S.sint[4], 1);
+            if (w == 0) {
+                while (__hip_atomic_load(&S.sint[4], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < 4)
+                    __builtin_amdgcn_s_sleep(1);
+                RAE_STAMP(a, 13);
+                float pz[NI], pp[NI];
+                fast_softmax<m, NSL, NI>(a, S, wbk, lane, pz, pp);
+                if (RAE_FWD_PFLAG) {
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    if (lane == 0) __hip_atomic_store(&S.sint[5], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+            } else {
+#ifdef RAE_WSTAMPS
+                RAE_WSTAMP_WAIT(0);          // waves 1-3 only poll from here: their last C register
+                RAE_WSTAMP_T(4);
 #endif
+                if (RAE_FWD_PFLAG)
+                    while (__hip_atomic_load(&S.sint[5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0)
+                        __builtin_amdgcn_s_sleep(1);
+            }
+            if (!RAE_FWD_PFLAG) lds_barrier();
+        }
+    }
+    if (general) {                           // both roles arrive behind the descriptor barrier
+        // waves 4-7 come with C and Ab loads in flight (no LDS-DMA): landed before the general
+        // path starts, so it begins with the registers free and nothing in flight
+        __builtin_amdgcn_s_waitcnt(RAE_WAIT_VM0);
         lds_barrier();
         sp_example<VM == 4, D>(a, g, bl, smem);
         return;
     }
-    if (a.values) {                          // non-binary features: their values
-        if (w < 4 && tid < nf) S.sfval[tid] = a.values[p0 + tid];
-        lds_barrier();
-    }
-    RAE_STAMP(a, 10);
-
-    // Per-CU issue order W rows -> A rows -> decoder matrices: vmcnt and the CU's memory
-    // queue are in issue order, so the 5 KB of W rows the chain waits on go out first, the
-    // A rows (needed after C.P) next, and the 160 KB of decoder matrices last.
-    // W rows (waves 0-3): slot = feature lane group, c = float4 column.
-    const MT* Wm = reinterpret_cast<const MT*>(a.W);
-    const int slot = tid / MV, c = tid - slot * MV;
-    MT wv[KF];
-    float fv[KF];
-    if (w < 4) {
-#pragma unroll
-        for (int k = 0; k < KF; ++k) {
-            const int f = slot + NSL * k;
-            const bool ok = slot < NSL && f < nf;
-            const int fi = RAE_KO_W ? 0 : S.sfidx[f < 256 ? f : 255];   // knockout: row 0
-            wv[k] = Wm[(int64_t)(ok ? fi : 0) * MV + c];
-            fv[k] = ok ? S.sfval[f < 256 ? f : 255] : 0.f;
-        }
-    }
-    lds_barrier();                           // every W-row load is issued
-    RAE_STAMP(a, 11);
-    // Each role is one uniform branch, so the compiler's vmcnt bookkeeping for the W-row
-    // FMAs sees only the 28 decoder-matrix loads behind them (not the DMA loop).
-    float abv = 0.f;
-#if RAE_FWD_CWAIT
-    // the decoder-matrix loads are issued by common code after the role branch: issued in one
-    // place, their registers need no copies where the role paths merge (copies of a loaded
-    // register wait for it, which had put a vmcnt(0) -- all of C -- in front of C.P)
-    if (w >= 4) {
-        // A rows by LDS-DMA, one row per wave instruction (r / 4 = 50 lanes x 16 B), rows
-        // w-4, w, w+4, ...: a fixed unrolled count (no loop, so the vmcnt bookkeeping of the
-        // C loads behind it stays exact)
-        static_assert(r / 4 <= RAE_WAVE, "one DMA instruction per A row");
-        constexpr int RPW4 = (NR + 3) / 4;
-        const int ln = lane < r / 4 ? lane : 0;
-#pragma unroll
-        for (int k = 0; k < RPW4; ++k) {
-            const int rho = (w - 4) + 4 * k;
-            if (rho < NR && lane < r / 4) {
-                const int j = rho == 0 ? 0 : rho + 1;            // SP: e2's row is not read
-                const float* src = a.A + (int64_t)(RAE_KO_A ? 0 : S.sids[j]) * r + (int64_t)ln * 4;
-                dma_row16(src, lds_addr(arows + rho * r4));
-            }
-        }
-        if (tid - 256 < NJ) abv = a.Ab[S.sids[tid - 256]];
-    }
     asm volatile("" ::: "memory");
-    if (!RAE_FWD_CEARLY47 || w < 4) cc_.load(a, Dm, 0, 0);
-    if (w < 4) {
-        MT acc;
-        vzero(acc);
-#pragma unroll
-        for (int k = 0; k < KF; ++k) vfma(acc, fv[k], wv[k]);
-        if (slot < NSL) reinterpret_cast<MT*>(S.spart)[slot * MV + c] = acc;
-    }
-    if (false) {
-#else
-    if (w < 4) {
-#endif
-        asm volatile("" ::: "memory");
-        cc_.load(a, Dm, 0, 0);
-        MT acc;
-        vzero(acc);
-#pragma unroll
-        for (int k = 0; k < KF; ++k) vfma(acc, fv[k], wv[k]);
-        if (slot < NSL) {
-#if !RAE_FWD_CWAIT
-            for (int f = slot + NSL * KF; f < nf; f += NSL)      // rows with > NSL*KF features
-                vfma(acc, S.sfval[f], Wm[(int64_t)S.sfidx[f] * MV + c]);
-#endif
-            reinterpret_cast<MT*>(S.spart)[slot * MV + c] = acc;
-        }
-    } else if (!RAE_FWD_CWAIT) {
-        gather_rows_dma<true>(a, Dm, S, NR, 1, 4, 4);
-        if (tid - 256 < NJ) abv = a.Ab[S.sids[tid - 256]];
-        asm volatile("" ::: "memory");
-        cc_.load(a, Dm, 0, 0);
-    }
-    RAE_STAMP(a, 12);
-    // S = X.W + Wb and the softmax run in wave 0 as soon as waves 0-3 have their partial
-    // sums in LDS (LDS arrival counter) -- not behind a block barrier, which would also
-    // wait for waves 4-7, still issuing (and back-pressured on) the bulk loads.
-    if (w < 4) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (lane == 0) atomicAdd(&S.sint[4], 1);
-    }
-    if (w == 0) {
-        while (__hip_atomic_load(&S.sint[4], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < 4)
-            __builtin_amdgcn_s_sleep(1);
-        RAE_STAMP(a, 13);
-        float pz[NI], pp[NI];
-        fast_softmax<m, NSL, NI>(a, S, wbk, lane, pz, pp);
-        if (RAE_FWD_PFLAG) {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            if (lane == 0) __hip_atomic_store(&S.sint[5], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
-    }
-    if (RAE_FWD_PFLAG) {
-        // P / Z / H ready: an LDS flag instead of a block barrier, so the waves that run the
-        // chain do not wait for waves 4-7 still issuing their bulk loads
-        if (w != 0)
-            while (__hip_atomic_load(&S.sint[5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0)
-                __builtin_amdgcn_s_sleep(1);
-        asm volatile("" ::: "memory");
-    } else {
-        lds_barrier();
-    }
     const float H = S.sred[40];
     RAE_STAMP(a, 2);
-#if RAE_FWD_CWAIT
+    RAE_WSTAMP_T(5);                         // P published (wave 0) / seen
     {
         // wC1 = C1.P, wC2 = C2.P: the 2*RA partial dots in C's load order (each waits for its
-        // own loads only), then the 2*RA group reductions as independent interleaved DPP
-        // chains, then one masked store block
+        // own loads only: ascending ra on either role, the early tranche first), then the 2*RA
+        // group reductions as independent interleaved DPP chains, then one masked store block
         typedef CCF CC_;
-        static_assert(CC_::FITS && CC_::CC <= 2, "fast path keeps C1/C2 in registers");
         const int gid = tid >> 4, q = tid & 15;
         const MT* Pv = reinterpret_cast<const MT*>(S.sP);
         MT pv[CC_::CC];
@@ -1215,9 +1280,7 @@ __device__ void sp_example_fast(const StepArgs& a, int64_t g, int bl, char* smem
             }
         }
     }
-#else
-    sp_project<true>(a, Dm, S, cc_);
-#endif
+    RAE_WSTAMP_T(6);                         // this wave's C.P done
     if (w >= 4 && tid - 256 < NJ) S.sAbv[tid - 256] = abv;
     dma_visible_barrier();                   // A rows (LDS-DMA) and Ab landed
     RAE_STAMP(a, 3);
@@ -1459,6 +1522,14 @@ __device__ void sp_example_fast(const StepArgs& a, int64_t g, int bl, char* smem
     RAE_STAMP(a, 7);
 #ifdef RAE_STAMPS
     if (a.stamps && threadIdx.x == 0) a.stamps[(size_t)blockIdx.x * 16 + 15] = __builtin_amdgcn_s_memtime();
+#endif
+#ifdef RAE_WSTAMPS
+    RAE_WSTAMP_T(7);
+    if (a.wstamps && lane == 0) {
+        unsigned long long* o = a.wstamps + ((size_t)blockIdx.x * RAE_FNW + w) * 8;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) o[k] = wst[k];
+    }
 #endif
 }
 

@@ -231,6 +231,12 @@ struct StepArgs {
     int privc;           // one workgroup per example (partitioned plans: ~1/G of the rows)
     int32_t* pmask;
     unsigned long long* stamps;   // diagnostic build only (RAE_STAMPS): phase timestamps
+    // RAE_WSTAMPS changes this struct, i.e. the kernels' argument layout: safe only because the
+    // host code that fills it and the kernels that read it are one translation unit (rae.hip),
+    // compiled with one set of flags -- never build one half with the flag and the other without
+#ifdef RAE_WSTAMPS
+    unsigned long long* wstamps;  // per-wave stamps of the fast SP forward, a buffer of their own
+#endif
 };
 
 // The global batch a step kernel works on: a device cursor + offset (graphs replayed over an
