@@ -313,16 +313,55 @@ def _decoder_forward_backward(decoder, p, P, H, e1, e2, neg1, neg2, D, bf16=Fals
     return pos, negs, dP, g
 
 
+def softmax_backward_pairwise(S, d, ce):
+    """dS of cost(P = softmax(S)) whose derivative with respect to P is d + ce (log P + 1), as
+    dS_k = P_k sum_j P_j (t_k - t_j), t = d + ce z, z = S - max S: every term of the sum is a
+    difference of two inputs times positive weights, so nothing cancels between large products
+    (the direct form P (dP - sum P dP) loses the rows whose dS is far below P |dP|, i.e. a
+    saturated P).  One example at a time (m^2 memory), in the dtype of S (float64, longdouble)."""
+    S = np.asarray(S)
+    d = np.asarray(d, dtype=S.dtype)
+    z = S - S.max(axis=1, keepdims=True)
+    e = np.exp(z)
+    P = e / e.sum(axis=1, keepdims=True)
+    t = d + S.dtype.type(ce) * z
+    dS = np.empty_like(S)
+    for b in range(S.shape[0]):
+        dS[b] = P[b] * ((t[b][:, None] - t[b][None, :]) @ P[b])
+    return dS
+
+
+def softmax_backward_centred(S, d, ce):
+    """The centred form the device kernels use, in the dtype of S:
+    z = S - max S, P = e^z / sum e^z, dS_k = P_k ((d_k - sum_j P_j d_j) + ce (z_k - sum_j P_j z_j))."""
+    S = np.asarray(S)
+    d = np.asarray(d, dtype=S.dtype)
+    ce = S.dtype.type(ce)
+    z = S - S.max(axis=1, keepdims=True)
+    e = np.exp(z)
+    P = e / e.sum(axis=1, keepdims=True)
+    dc = d - (P * d).sum(axis=1, keepdims=True)
+    zc = z - (P * z).sum(axis=1, keepdims=True)
+    return P * (dc + ce * zc)
+
+
+SOFTMAX_BACKWARDS = {"pairwise": softmax_backward_pairwise, "centred": softmax_backward_centred}
+
+
 def train_step_grads(decoder: str, p: dict, X, e1, e2, neg1, neg2, *, alpha: float,
                      lambda1: float = 0.0, lambda2: float = 0.0, adjust: float = 0.0,
                      ext_reg: bool = True, denom: float | None = None,
-                     bf16: bool = False) -> StepResult:
+                     bf16: bool = False, softmax_backward: str = "direct") -> StepResult:
     """Forward + loss + dense gradients of one ``func['train']`` call.
 
     cost = -mean(all_scores) + lambda1*adjust*L1 + lambda2*adjust*L2
     (learning/OieModel.py:90, learning/OieInduction.py:131-135), all_scores =
     [logsig(u) (2l), H (l), H (l), logsig(-g) (2ls)] (SelectionalPreferences.py:39,50;
     Bilinear.py:39,48; BilinearPlusSP.py:47,56).
+
+    softmax_backward: "direct" (the default) is P (dP - sum P dP); "pairwise" and "centred"
+    (softmax_backward_pairwise / _centred) restate it for saturated P.  Everything is computed
+    in the dtype of the parameters and X, so float32 inputs give a float32 host step.
     """
     e1 = np.asarray(e1, dtype=np.int64)
     e2 = np.asarray(e2, dtype=np.int64)
@@ -341,8 +380,11 @@ def train_step_grads(decoder: str, p: dict, X, e1, e2, neg1, neg2, *, alpha: flo
     assert scores.shape[0] == 4 * l + 2 * l * s
     cost = -float(scores.sum()) / D                         # OieModel.py:90 (mean)
     # entropy: cost has -(2/D) * sum_b H_b; dH_b/dP_bk = -alpha (logP_bk + 1)
-    dP = dP + (2.0 * alpha / D) * (logP + 1.0)
-    dS = P * (dP - (P * dP).sum(axis=1, keepdims=True))     # softmax backward
+    if softmax_backward == "direct":
+        dP = dP + (2.0 * alpha / D) * (logP + 1.0)
+        dS = P * (dP - (P * dP).sum(axis=1, keepdims=True))     # softmax backward
+    else:
+        dS = SOFTMAX_BACKWARDS[softmax_backward](S, dP, 2.0 * alpha / D)
     g["W"] = np.asarray(X.T @ dS)
     g["Wb"] = dS.sum(axis=0)
     # regularisers (OieInduction.py:131-135)

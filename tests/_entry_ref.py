@@ -18,6 +18,7 @@ from test_gpu_eval import COST_RTOL, TERM_ATOL, TERM_RTOL, _group as group
 
 PROB_RTOL, PROB_ATOL = 1e-4, 1e-6
 MARGIN = 1e-4                       # labels compared where the oracle's top-2 margin exceeds it
+LABEL_MARGIN = 1e-5                 # ... test_gpu_fullscale.check_labels' margin (the trained split)
 
 DEC_ID = {"sp": 0, "rescal": 1, "rescal+sp": 2}
 EDGE_NNZ = [0, 1, 17, 64, 65, 130]

@@ -3,7 +3,8 @@ test_gpu_eval_ranges), checked on the CPU: a float32 numpy restatement of the fo
 (tests/_entry_ref.py) must agree with the float64 oracle within HALF of the tolerances the
 kernels are held to, at every shape of the matrices -- so a plain float32 evaluation of these
 inputs has room to spare and a kernel that misses a tolerance is wrong, not unlucky.  The share
-of label rows the top-2 margin filter leaves out is bounded here as well.  No GPU needed."""
+of label rows the top-2 margin filter leaves out is bounded here as well.  The saturated parameters of tests/_grad_ref.py get the same check.  No GPU
+needed."""
 import numpy as np
 import pytest
 
@@ -47,3 +48,35 @@ def test_label_inputs(m):
     np.testing.assert_allclose(P.astype(np.float64), want_p, rtol=E.PROB_RTOL / 2,
                                atol=E.PROB_ATOL / 2)
     assert (~clear).mean() <= S.MAX_UNCLEAR
+
+
+@pytest.mark.parametrize("shape", S.SAT_ENTRY_SHAPES)
+def test_saturated_entry_inputs(shape):
+    """The saturated parameters through the forward-only entries: the float32 restatement holds
+    half the kernels' tolerances on terms, cost and probabilities, the terms are finite, some
+    shifted logit is below -87.3 at the x 8 shapes, and at least 90 % of the rows have a
+    decisive label (check_labels' margin)."""
+    prob = S.sat_problem(shape)
+    E.check_inputs_f32(prob, 0, prob.N, f"saturated {shape}")
+    assert np.isfinite(prob.oracle_terms(0, prob.N)).all()
+    W, Wb = prob.p32["W"], prob.p32["Wb"]
+    Sc, P32, _ = E.f32_encoder(prob.X, W, Wb)
+    _, want_p = E.O.label(prob.X, W.astype(np.float64), Wb.astype(np.float64))
+    np.testing.assert_allclose(P32.astype(np.float64), want_p, rtol=E.PROB_RTOL / 2,
+                               atol=E.PROB_ATOL / 2)
+    S64 = np.asarray(prob.X.astype(np.float64) @ W.astype(np.float64)) + Wb
+    srt = np.sort(S64, axis=1)
+    assert ((srt[:, -1] - srt[:, -2]) > E.LABEL_MARGIN).mean() >= 0.9
+    if shape != "S1":
+        assert (S64 - srt[:, -1:] < -87.3).any()
+
+
+@pytest.mark.parametrize("shape", [s for s, scores in S.SAT_ENTRY_CASES if scores])
+def test_saturated_scores_entry_inputs(shape):
+    """... and the variant whose decoder scores saturate (A, Ab x 32): the float32 restatement
+    holds half the kernels' tolerances, the terms are finite, and some per-example term is
+    beyond -87 (a score past the point where fp32 sigmoid is exactly 0)."""
+    prob = S.sat_problem(shape, scores=True)
+    E.check_inputs_f32(prob, 0, prob.N, f"saturated-scores {shape}")
+    terms = prob.oracle_terms(0, prob.N)
+    assert np.isfinite(terms).all() and terms[:, [0, 2]].min() < -87.0

@@ -20,7 +20,8 @@ one rank, and for each of three batches
 
 A data-parallel form differs from the single-rank step at the same global batch in summation
 order only (the ranks' blocks are added in rank order), which the factor 16 already covers.
-Every COST / RATIO line is printed; profiles/dp_options_grad_check.txt keeps the table.
+Every COST / RATIO line is printed; profiles/dp_options_grad_check.txt keeps the table (the
+limit shapes U1, U2 and U4 at two ranks: profiles/limit_shapes_grad_check.txt).
 
 k_bil_prep (the bf16 R-gradient operands laid out by a kernel after the exchange, which every
 data-parallel bf16 plan runs) is also pinned at a single rank against the forward-fused layout,

@@ -8,6 +8,9 @@ pass from r = 17 / r = 68; eval_project has scalar and float4 k-tails and more j
 from r = 33; the negative loop takes 8 tasks per round.  Every case below names the edge it is
 there for.  tests/test_entry_inputs.py checks the inputs of every case on the CPU.
 
+The saturated parameters of tests/_grad_ref.py (W, Wb x 8 or x 3, A, Ab x 2: P one-hot, shifted
+logits down to -190) go through both entries as well, at the shapes S1, S3, B2 and H1.
+
 Tolerances are the project's own (test_gpu_eval, test_label_pass_matches_oracle): cost
 2e-5 max(1, |c|); terms rtol 1e-4, atol 1e-5; label probabilities rtol 1e-4, atol 1e-6; labels
 equal where the oracle's top-2 margin exceeds 1e-4.
@@ -40,6 +43,7 @@ EVAL_SHAPES = {
     "sp-m33-r17-s5": ("sp", 33, 17, 5),       # mv = 33: LPR 64 scalar; scalar second pass; 2s = 10
     "sp-m65-r40-s3": ("sp", 65, 40, 3),       # mv = 65: NQ = 2 scalar; 6 jobs over 4 waves
     "sp-m127-r13-s3": ("sp", 127, 13, 3),     # the largest scalar m, NQ = 2
+    "sp-m127-r125-s3": ("sp", 127, 125, 3),   # ... with the largest scalar r: two per lane in both
     "sp-m16-r3-s1": ("sp", 16, 3, 1),         # mv = 4 float4 next to the scalar r
     # SP, float4 encoder: mv = 1, 16 | 17, 32 | 33, 64 | 65, 128
     "sp-m4-r4-s1": ("sp", 4, 4, 1),           # mv = 1; float4 eval_dot rv = 1; float4 k-tail
@@ -60,13 +64,18 @@ EVAL_SHAPES = {
 }
 
 
+# shapes added after the seeds were given out (a shape's seed is its rank among the others)
+EVAL_ADDED = ["sp-m127-r125-s3"]
+_EVAL_SEEDS = sorted(k for k in EVAL_SHAPES if k not in EVAL_ADDED) + EVAL_ADDED
+
+
 def eval_problem(name):
     dec, m, r, s = EVAL_SHAPES[name]
     g = np.random.RandomState(7)
     lens = np.concatenate([g.randint(0, 12, ROW0 + 2), E.EDGE_NNZ,
                            g.randint(0, 12, NROWS - 2 - len(E.EDGE_NNZ))])
     assert len(lens) == ROW0 + NROWS
-    return E.EvalProblem(dec, m, r, s, lens, n=30, d=400, seed=sorted(EVAL_SHAPES).index(name))
+    return E.EvalProblem(dec, m, r, s, lens, n=30, d=400, seed=_EVAL_SEEDS.index(name))
 
 
 @pytest.mark.parametrize("name", list(EVAL_SHAPES))
@@ -105,15 +114,12 @@ def label_oracle(X, W, Wb):
     return lab, P, (srt[:, -1] - srt[:, -2]) > E.MARGIN
 
 
-@pytest.mark.parametrize("m", LABEL_M)
-def test_label_lane_maps(built_lib, cuda_dev, m):
+def _device_labels(built_lib, cuda_dev, X, W, Wb, row0, nrows):
+    """rae_label on rows [row0, row0 + nrows), with and without probabilities: (labels, the
+    labels of the call without probabilities, probabilities) as numpy arrays."""
     import torch
     from rae import _lib
-    X, W, Wb = label_problem(m)
-    n = X.shape[0]
-    row0, nrows = LABEL_ROW0, n - LABEL_ROW0
-    want_lab, want_p, clear = label_oracle(X, W, Wb)
-    assert (~clear).mean() <= MAX_UNCLEAR
+    n, m = X.shape[0], W.shape[1]
     up = lambda x: torch.as_tensor(np.ascontiguousarray(x), device=cuda_dev)
     indptr, indices = up(X.indptr.astype(np.int32)), up(X.indices.astype(np.int32))
     values, Wt, Wbt = up(X.data.astype(np.float32)), up(W), up(Wb)
@@ -128,7 +134,17 @@ def test_label_lane_maps(built_lib, cuda_dev, m):
     _lib.check(built_lib.rae_label(p(indptr), p(indices), p(values), p(Wt), p(Wbt), m, row0,
                                    nrows, p(lab2), None, None))
     torch.cuda.synchronize()
-    lab, lab2, pr = lab.cpu().numpy(), lab2.cpu().numpy(), pr.cpu().numpy()
+    return lab.cpu().numpy(), lab2.cpu().numpy(), pr.cpu().numpy()
+
+
+@pytest.mark.parametrize("m", LABEL_M)
+def test_label_lane_maps(built_lib, cuda_dev, m):
+    X, W, Wb = label_problem(m)
+    n = X.shape[0]
+    row0, nrows = LABEL_ROW0, n - LABEL_ROW0
+    want_lab, want_p, clear = label_oracle(X, W, Wb)
+    assert (~clear).mean() <= MAX_UNCLEAR
+    lab, lab2, pr = _device_labels(built_lib, cuda_dev, X, W, Wb, row0, nrows)
     assert (lab[nrows:] == -7).all() and (pr[nrows:] == -7.0).all()
     assert np.array_equal(lab, lab2)
     err = np.abs(pr[:nrows] - want_p[row0:])
@@ -137,3 +153,66 @@ def test_label_lane_maps(built_lib, cuda_dev, m):
     ok = clear[row0:]
     assert lab[:nrows].min() >= 0 and lab[:nrows].max() < m
     assert np.array_equal(lab[:nrows][ok], want_lab[row0:][ok])
+
+
+# ------------------------------------------- D. the forward-only entries on saturated parameters
+SAT_ENTRY_SHAPES = ["S1", "S3", "B2", "H1"]
+# the variant with saturated scores (A, Ab x 32) where a float32 evaluation of the inputs keeps
+# half the tolerances (tests/test_entry_inputs.py); at H1 it does not: one term of 1.8e4, a sum of
+# cancelling bilinear and SP parts, is 8.7e-5 off in float32 numpy
+SAT_ENTRY_CASES = [(s, False) for s in SAT_ENTRY_SHAPES] + [(s, True) for s in ("S1", "S3", "B2")]
+
+
+def sat_problem(shape, scores=False):
+    """The train split of tests/_grad_ref.py's case (shape, O3) -- three batches, non-binary
+    feature values -- with its saturated parameters (W, Wb x 8 or x 3, A, Ab x 2: P one-hot to
+    1e-4, shifted logits down to -100 ... -190), as an EvalProblem.  scores: A, Ab x 32, the
+    variant whose decoder scores pass +-87."""
+    import _grad_ref as G
+    c = G.case_config(shape, "O3", regime="saturated-scores" if scores else "saturated")
+    data, neg1, neg2 = G.case_dataset(c)
+    xs = data.split["train"]
+    prob = E.EvalProblem.__new__(E.EvalProblem)
+    prob.dec, prob.m, prob.r, prob.s = c["dec"], c["m"], c["r"], c["s"]
+    prob.n, prob.d, prob.alpha = c["n"], c["d"], c["alpha"]
+    prob.X = xs.xFeats.astype(np.float32).tocsr()
+    prob.N = prob.stride = prob.X.shape[0]
+    prob.a1, prob.a2 = xs.args1.astype(np.int32), xs.args2.astype(np.int32)
+    prob.n1, prob.n2 = np.ascontiguousarray(neg1, np.int32), np.ascontiguousarray(neg2, np.int32)
+    prob.p32 = dict(G.generic_params(c))
+    prob.p64 = {k: v.astype(np.float64) for k, v in prob.p32.items()}
+    return prob
+
+
+@pytest.mark.parametrize("shape,scores", SAT_ENTRY_CASES,
+                         ids=[s + ("-scores" if v else "") for s, v in SAT_ENTRY_CASES])
+def test_eval_cost_saturated(built_lib, cuda_dev, shape, scores):
+    """rae_eval_cost over the whole split at the saturated parameters: per-example terms and the
+    cost against float64 at this module's tolerances.  "scores": A, Ab x 32, decoder scores
+    beyond +-87 (the log sigmoids are then the scores themselves, or 0)."""
+    prob = sat_problem(shape, scores)
+    dev = E.DeviceEval(built_lib, prob, cuda_dev)
+    want = prob.oracle_terms(0, prob.N)
+    out, sums = dev.run(0, prob.N, terms=True)
+    assert np.isfinite(out.cpu().numpy()).all() and np.isfinite(sums).all()
+    E.check_eval(out, sums, want, prob.s, f"saturated {shape}")
+
+
+@pytest.mark.parametrize("shape", SAT_ENTRY_SHAPES)
+def test_label_saturated(built_lib, cuda_dev, shape):
+    """rae_label at the saturated parameters: labels by check_labels' margin rule (equal to the
+    oracle's wherever its top-2 margin exceeds LABEL_MARGIN, at least 90 % of the rows
+    decisive), probabilities at this module's tolerances -- the oracle's underflow to exactly 0
+    where the device's __expf does, within PROB_ATOL."""
+    from types import SimpleNamespace
+    from test_gpu_fullscale import check_labels
+    prob = sat_problem(shape)
+    W, Wb = prob.p32["W"], prob.p32["Wb"]
+    lab, lab2, pr = _device_labels(built_lib, cuda_dev, prob.X, W, Wb, 0, prob.N)
+    assert np.array_equal(lab, lab2) and lab.min() >= 0 and lab.max() < prob.m
+    check_labels(lab, SimpleNamespace(xFeats=prob.X), W.astype(np.float64), Wb.astype(np.float64),
+                 what=f"saturated {shape}")
+    _, want_p = E.O.label(prob.X, W.astype(np.float64), Wb.astype(np.float64))
+    assert np.isfinite(pr).all()
+    print(f"saturated {shape}: max |dprob| {np.abs(pr - want_p).max():.3e}")
+    np.testing.assert_allclose(pr, want_p, rtol=E.PROB_RTOL, atol=E.PROB_ATOL)

@@ -23,7 +23,8 @@ COST_RTOL = 2e-5
 
 
 LABEL_ROWS = 100_000      # rows of the trained split the relation assignments are checked on
-LABEL_MARGIN = 1e-5       # labels compared where the oracle's top-2 score margin exceeds this
+from _entry_ref import LABEL_MARGIN     # noqa: E402  (1e-5: labels are compared where the
+#                                         oracle's top-2 score margin exceeds it)
 
 
 def _gpu_labels(eng, nrows=LABEL_ROWS):

@@ -16,7 +16,21 @@ run, and
   bf16       test_gpu_fullscale.check_bf16's rule on rho: rho(gpu, exact) <= 1.25 rho(emu, exact)
              + t and rho(gpu, emu) <= 0.25 rho(emu, exact) + t, t the fp32 tolerance above (the
              AdaGrad sign rule is applied against each reference with that reference's bound);
-  forms      kernel_forms_in_use() shows the intended form.
+  forms      kernel_forms_in_use() shows the intended form;
+  limits     the shapes U1-U8 sit at the upper end of what plan_resolve accepts: m = r = 512
+             (eight softmax slots per lane of wave 0; the split SP forward), 65 ... 128 columns
+             that are no multiple of 4 (two scalar elements per lane), the largest s at
+             m = r = 512, the bilinear decoders at m = 512 (bf16: M in fp32 above m = 128);
+  saturated  ("-sat") the same parameters with W, Wb x 8 (x 3 at the C3 / C5 shapes) and A,
+             Ab x 2: P is one-hot to 1e-4, shifted logits reach -100 ... -200 (__expf
+             underflows).  There float32 autograd's W is 1.0 from float64 in rho and the
+             oracle's own P (dP - sum P dP) 2.7e-5, so the truth of W / Wb is the pairwise
+             form (rae_oracle.softmax_backward_pairwise), rho divides by max(rowmax |g|,
+             2^-10 max |g| of the tensor), and the yardstick is the better of float32 autograd
+             and a float32 numpy restatement of the kernels' centred formula; cost, AdaGrad
+             step and untouched-row rules are unchanged, and everything must be finite.
+             The decoder's scores stay below 20 there; "-satu" (A, Ab x 32) puts 8 ... 93 % of
+             them beyond +-87 (asserted per batch), past sigmoid_softplus's linear branch.
 
 The yardstick is the float32 host's distance from float64 at the same parameters (measured
 7e-8 ... 1e-5; up to 8.8e-4 on W where P saturates), not the code under test; the factor 16 covers __expf / __logf / rcp argument
@@ -95,17 +109,20 @@ def _one_step_states(c, dev, forms=None, per_call=False):
 
 VARIANTS = [(s, o, None, False) for s, o in G.CASES] + [
     ("S1", "O0", "on", False), ("S1", "O0", "off", False),      # private rows on / off
-    ("S3", "O1", None, True), ("H1", "O4", None, True)]          # func['train'], the per-call ABI
+    ("S3", "O1", None, True), ("H1", "O4", None, True)] + [      # func['train'], the per-call ABI
+    (s, o, None, False, "saturated") for s, o in G.SAT_CASES] + [     # W, Wb x 8 (3), A, Ab x 2
+    (s, o, None, False, "saturated-scores") for s, o in G.SAT_SCORE_CASES]     # ... A, Ab x 32
 
 
 def _vid(v):
-    return f"{v[0]}-{v[1]}" + (f"-priv_{v[2]}" if v[2] else "") + ("-percall" if v[3] else "")
+    return (f"{v[0]}-{v[1]}" + (f"-priv_{v[2]}" if v[2] else "") + ("-percall" if v[3] else "") +
+            ({"saturated": "-sat", "saturated-scores": "-satu"}[v[4]] if v[4:] else ""))
 
 
 @pytest.mark.parametrize("variant", VARIANTS, ids=[_vid(v) for v in VARIANTS])
 def test_one_step_state_vs_reference(built_lib, cuda_dev, variant):
-    shape, option, priv, per_call = variant
-    c = G.case_config(shape, option)
+    shape, option, priv, per_call = variant[:4]
+    c = G.case_config(shape, option, regime=variant[4] if variant[4:] else "generic")
     forms = {"priv_rows": priv} if priv else None
     states, used = _one_step_states(c, cuda_dev, forms, per_call)
     want = _expected_forms(c)
