@@ -526,6 +526,71 @@ int rae_eval_topk(const rae_eval_args* a, const rae_topk_out* out, rae_stream_t 
  * top = 32; rae_eval_topk adds rae_eval_rank's query buffers of one round of rows.             */
 int64_t rae_topk_workspace_bytes(const rae_topk_args* q, const rae_eval_args* e, int32_t top);
 
+/* --- relation scores from the decoder: which relation do the two arguments themselves support
+ * (no reference counterpart: the reference contracts the encoder's P into the decoder first) ---- */
+/* psi_k(e1, e2), a1 = A[e1], a2 = A[e2]:
+ *     sp          <C1[:,k], a1> + <C2[:,k], a1>     (the reference's A[args1]-twice behaviour, as the
+ *                                                    objective scores it: psi does not depend on e2)
+ *     rescal      a1^T R3[:,:,k] a2
+ *     rescal+sp   a1^T R3[:,:,k] a2 + <C1[:,k], a1> + <C2[:,k], a2>
+ * so sum_k P_k psi_k is rae_eval_rank's `one`; the entity biases are not part of psi.
+ * rae_relation_scores: psi_out[q * ldp + k] for nq caller-given pairs; columns [relations, ldp) are
+ * never written.  A pair with an id outside [0, n_entities) gets a row of NaN: nothing is read out
+ * of range and no other row is disturbed.  Exact fp32 on v_mfma_f32_16x16x4_f32 whatever operands
+ * training ran with; the outer product a1 a2^T is formed in registers and never stored.
+ * A row's psi is a function of the row's own operands and of (decoder, embed, relations) alone:
+ * bitwise independent of nq, of the row's position and of the other rows, and the same from
+ * rae_relation_scores and rae_eval_relations for the same (e1, e2).  The contraction is not split:
+ * one value is one accumulator chain over the contraction rows (R3's (i, j) rows, then C1's, then
+ * C2's) in slabs of TK rows in ascending order, TK = 128 / 64 / 32 for relations <= 16 / <= 128 /
+ * above; step s = 4 q + e < TK / 4 of a slab adds its rows 16 q + 4 g + e, g = 0..3, in one
+ * instruction: an order fixed by relations alone.  No atomics.
+ * Every pointer is a device pointer except the struct.  Plan-free, stream-ordered, capturable:
+ * allocates nothing, never synchronises, writes only psi_out (and, rae_eval_relations, its outputs
+ * and the workspace); arguments are checked before the first HIP call.  nq == 0 is valid, reads no
+ * pointer and writes nothing.
+ * Limits: rae_eval_cost's shapes (relations <= 512, a multiple of 4 above 128, <= 320 for the
+ * bilinear decoders; embed <= 1024; C1 / C2 / R3 16-byte aligned when relations % 4 == 0); the
+ * kernel's own budget adds nothing (at most 84 KiB of LDS, at relations = 320); 1 <= n_entities <
+ * 2^31, ldp >= relations.  rae_relation_scores needs no workspace (rae_relscore_workspace_bytes
+ * gives 0): workspace may be NULL, and must be 256-byte aligned when it is not.  Long lists run in
+ * rounds of 16384 pairs.                                                                        */
+typedef struct rae_relscore_args {
+    int32_t decoder;            /* RAE_DEC_*                                                   */
+    int32_t relations, embed;   /* m, r                                                        */
+    int64_t n_entities;
+    const float *A, *C1, *C2, *R3;   /* unused ones may be NULL                               */
+    const int32_t *e1, *e2;     /* (nq)                                                        */
+    int64_t nq;
+    float *psi_out; int64_t ldp;
+    void *workspace; int64_t workspace_bytes;
+} rae_relscore_args;
+int rae_relation_scores(const rae_relscore_args* a, rae_stream_t stream);
+
+/* rae_eval_relations: rows [row0, row0+nrows) of a split at the current parameters, (e1, e2) =
+ * (args1, args2) of the row.  Per row, with S = x W + Wb:
+ *     psi_k                        as above
+ *     l_k = logsig(psi_k + Ab[e1]) + logsig(psi_k + Ab[e2])   (rae_eval_cost's pos term at the
+ *                                                    one-hot relation k, the same -softplus form)
+ *     joint_k = logsoftmax_k(S) + l_k,  the log-softmax as z_k - log sum exp z with z = S - max S
+ *               (never the log of a rounded P: finite for every finite logit)
+ *     labels_dec = argmax_k psi_k      labels_joint = argmax_k joint_k
+ * both the first maximum, NaN counting as the maximum (rae_label's rule).  Any of the four outputs
+ * may be NULL, not all of them.  Reads the fields of `a` that rae_eval_rank reads (Ab included);
+ * shape limits and alignment as rae_eval_cost.  Rows run in rounds of 16384; when psi is NULL the
+ * round's psi lives in the workspace.  A row's outputs are bitwise independent of row0, nrows and
+ * the other rows.  nrows == 0 is valid and writes nothing.                                      */
+typedef struct rae_rel_out {
+    float *psi, *joint;                 /* (nrows, relations), each may be NULL                */
+    int64_t *labels_dec, *labels_joint; /* (nrows), each may be NULL                           */
+} rae_rel_out;
+int rae_eval_relations(const rae_eval_args* a, const rae_rel_out* out, rae_stream_t stream);
+
+/* bytes of workspace of rae_relation_scores (q, with e NULL: 0) or of rae_eval_relations (e, with q
+ * NULL: one round's psi and log-softmax); host only, no HIP call; -1 on a bad argument or unless
+ * exactly one is given.  Reads the shapes only; independent of nq / nrows.                      */
+int64_t rae_relscore_workspace_bytes(const rae_relscore_args* q, const rae_eval_args* e);
+
 /* --- cluster evaluation (get_clusters_sets learning/OieInduction.py:321-340;
  *     evaluation/OieEvaluation.py:23-44,90-127) ------------------------------------ */
 /* Plan-free and stream-ordered like rae_label / rae_eval_cost: every pointer is a device

@@ -35,6 +35,7 @@
 #include "rae_p2p.hpp"
 #include "rae_profile.hpp"
 #include "rae_rank.hpp"
+#include "rae_relscore.hpp"
 #include "rae_topk.hpp"
 #include "rae_sampler.hpp"
 #include "rae_sp.hpp"
@@ -611,6 +612,15 @@ __global__ __launch_bounds__(RAE_ETK_FQ * 64) void k_topk_finish(const rae_key64
     __shared__ rae_key64 sList[RAE_ETK_FQ * 32];
     topk_finish(keys, strips, nq, top, ents, scores, sList);
 }
+
+// ---- relation scores from the decoder (rae_relscore.hpp) ----
+template <int NTA, int NTB, int TK>
+__global__ __launch_bounds__(RAE_RS_BT) void k_relscore(RelArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    rel_scores<NTA, NTB, TK>(a, reinterpret_cast<float*>(smem));
+}
+__global__ __launch_bounds__(RAE_RS_EBT) void k_rel_enc(RelEnc a) { rel_enc(a); }
+__global__ __launch_bounds__(RAE_RS_EBT) void k_rel_fin(RelFin a) { rel_fin(a); }
 
 __global__ void k_add_cursor(int64_t* cursor, int64_t count) {
     if (threadIdx.x == 0 && blockIdx.x == 0) *cursor += count;
@@ -2000,6 +2010,173 @@ extern "C" int rae_eval_topk(const rae_eval_args* a, const rae_topk_out* out, ra
                                        out->ents + 2 * c0 * top,
                                        out->scores ? out->scores + 2 * c0 * top : nullptr, st))
             return rc;
+    }
+    return RAE_OK;
+}
+
+// ---- relation scores from the decoder -----------------------------------------------------------
+namespace {
+struct RelLayout { size_t o_psi, o_lsm, total; };
+// the shapes of the relation-score kernel (host only): rae_eval_cost's limits
+int rel_shapes(int dec, int m, int r, int64_t n_entities) {
+    if (dec < 0 || dec > 2) return fail(RAE_E_INVALID, "decoder must be 0..2");
+    if (m < 1 || m > 512) return fail(RAE_E_INVALID, "relations must be in [1, 512]");
+    if ((m % 4) != 0 && m > 128)
+        return fail(RAE_E_INVALID, "relations must be a multiple of 4 above 128");
+    if (r < 1 || r > 1024) return fail(RAE_E_INVALID, "embed must be in [1, 1024]");
+    if (dec != RAE_DEC_SP && m > 320)
+        return fail(RAE_E_INVALID, "relations must be <= 320 for the bilinear decoders");
+    if (n_entities < 1 || n_entities >= (1ll << 31))
+        return fail(RAE_E_INVALID, "n_entities must be in [1, 2^31)");
+    return RAE_OK;
+}
+int eval_rel_layout(const rae_eval_args* a, RelLayout& L) {
+    if (const int rc = eval_shapes(a, false)) return rc;
+    if (const int rc = rel_shapes(a->decoder, a->relations, a->embed, a->n_entities)) return rc;
+    const size_t per = ev_align((size_t)RAE_RS_ROUND * a->relations * sizeof(float));
+    L.o_psi = 0; L.o_lsm = per; L.total = 2 * per;
+    return RAE_OK;
+}
+template <int NTA, int NTB, int TK>
+int rel_launch_cfg(const RelArgs& k, dim3 grid, size_t lds, hipStream_t st) {
+    if (lds > 48 * 1024)         // large dynamic LDS is opted into per kernel (not a stream operation)
+        HIPCHK(hipFuncSetAttribute((const void*)k_relscore<NTA, NTB, TK>,
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((k_relscore<NTA, NTB, TK>), grid, dim3(RAE_RS_BT), lds, st, k);
+    return RAE_OK;
+}
+// one round (k.nq <= RAE_RS_ROUND pairs) on the stream
+int rel_launch(RelArgs k, hipStream_t st) {
+    const int m = k.m, r = k.r;
+    k.KR = k.dec == RAE_DEC_SP ? 0 : r * r;
+    k.K = k.KR + (k.dec == RAE_DEC_RESCAL ? 0 : 2 * r);
+    k.rinv = r > 1 ? (unsigned)((1ull << 32) / (unsigned)r) + 1u : 0u;
+    k.av4 = (r % 4) == 0 && ((uintptr_t)k.A & 15) == 0;
+    const RelConfig c = rel_config(m);
+    const dim3 grid((unsigned)ceil_div(k.nq, rel_block_examples(c)),
+                    (unsigned)ceil_div(m, rel_group_cols(c)));
+    const size_t lds = rel_lds_bytes(c);
+    switch (c.nta + c.ntb) {                 // the cases of rel_config
+    case 1: return rel_launch_cfg<1, 0, 128>(k, grid, lds, st);
+    case 2: return rel_launch_cfg<1, 1, 64>(k, grid, lds, st);
+    case 4: return rel_launch_cfg<2, 2, 64>(k, grid, lds, st);
+    case 7: return rel_launch_cfg<4, 3, 64>(k, grid, lds, st);
+    case 8: return rel_launch_cfg<4, 4, 64>(k, grid, lds, st);
+    case 12: return rel_launch_cfg<6, 6, 32>(k, grid, lds, st);
+    case 16: return rel_launch_cfg<8, 8, 32>(k, grid, lds, st);
+    default: return rel_launch_cfg<10, 10, 32>(k, grid, lds, st);
+    }
+}
+}  // namespace
+
+extern "C" int64_t rae_relscore_workspace_bytes(const rae_relscore_args* q, const rae_eval_args* e) {
+    if ((q != nullptr) == (e != nullptr))
+        return fail(RAE_E_INVALID, "give exactly one of the two argument structs"), -1;
+    if (q) {
+        if (rel_shapes(q->decoder, q->relations, q->embed, q->n_entities)) return -1;
+        return 0;
+    }
+    RelLayout L;
+    if (eval_rel_layout(e, L)) return -1;
+    return (int64_t)L.total;
+}
+
+extern "C" int rae_relation_scores(const rae_relscore_args* a, rae_stream_t stream) {
+    if (!a) return fail(RAE_E_INVALID, "null argument");
+    if (const int rc = rel_shapes(a->decoder, a->relations, a->embed, a->n_entities)) return rc;
+    if (a->nq < 0) return fail(RAE_E_INVALID, "nq must be >= 0");
+    if (a->ldp < a->relations) return fail(RAE_E_INVALID, "ldp is smaller than relations");
+    if (a->workspace_bytes < 0) return fail(RAE_E_INVALID, "workspace_bytes must be >= 0");
+    if ((uintptr_t)a->workspace & 255) return fail(RAE_E_INVALID, "workspace must be 256-byte aligned");
+    if (a->nq == 0) return RAE_OK;            // nothing is read or written
+    const int m = a->relations, r = a->embed;
+    const bool bil = a->decoder != RAE_DEC_SP;
+    if (!a->A) return fail(RAE_E_INVALID, "A is NULL");
+    if (a->decoder != RAE_DEC_RESCAL && (!a->C1 || !a->C2))
+        return fail(RAE_E_INVALID, "C1 / C2 is NULL");
+    if (bil && !a->R3) return fail(RAE_E_INVALID, "R3 is NULL");
+    if (!a->e1 || !a->e2) return fail(RAE_E_INVALID, "e1 / e2 is NULL");
+    if (!a->psi_out) return fail(RAE_E_INVALID, "psi_out is NULL");
+    if ((m % 4) == 0 && (((uintptr_t)a->C1 | (uintptr_t)a->C2 | (uintptr_t)a->R3) & 15))
+        return fail(RAE_E_INVALID, "C1 / C2 / R3 must be 16-byte aligned");
+    if (((uintptr_t)a->A | (uintptr_t)a->psi_out | (uintptr_t)a->e1 | (uintptr_t)a->e2) & 3)
+        return fail(RAE_E_INVALID, "A / psi_out / e1 / e2 must be 4-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    for (int64_t c0 = 0; c0 < a->nq; c0 += RAE_RS_ROUND) {
+        RelArgs k;
+        k.dec = a->decoder; k.m = m; k.r = r;
+        k.A = a->A; k.C1 = a->C1; k.C2 = a->C2; k.R3 = a->R3;
+        k.e1 = a->e1 + c0; k.e2 = a->e2 + c0; k.n_ent = a->n_entities;
+        k.nq = (int)std::min<int64_t>(RAE_RS_ROUND, a->nq - c0);
+        k.psi = a->psi_out + c0 * a->ldp; k.ldp = a->ldp;
+        if (const int rc = rel_launch(k, st)) return rc;
+        HIPCHK(hipGetLastError());
+    }
+    return RAE_OK;
+}
+
+extern "C" int rae_eval_relations(const rae_eval_args* a, const rae_rel_out* out, rae_stream_t stream) {
+    RelLayout L;
+    if (const int rc = eval_rel_layout(a, L)) return rc;
+    if (!out) return fail(RAE_E_INVALID, "out is NULL");
+    if (!out->psi && !out->joint && !out->labels_dec && !out->labels_joint)
+        return fail(RAE_E_INVALID, "all four outputs are NULL");
+    if (a->nrows < 0) return fail(RAE_E_INVALID, "nrows must be >= 0");
+    if (a->row0 < 0 || a->row0 + a->nrows >= (1ll << 31))
+        return fail(RAE_E_INVALID, "row0 / nrows out of range");
+    const int m = a->relations, r = a->embed;
+    const bool bil = a->decoder != RAE_DEC_SP, v4 = (m % 4) == 0;
+    if (!a->W) return fail(RAE_E_INVALID, "W is NULL");
+    if (!a->Wb) return fail(RAE_E_INVALID, "Wb is NULL");
+    if (!a->A) return fail(RAE_E_INVALID, "A is NULL");
+    if (!a->Ab) return fail(RAE_E_INVALID, "Ab is NULL");
+    if (a->decoder != RAE_DEC_RESCAL && (!a->C1 || !a->C2))
+        return fail(RAE_E_INVALID, "C1 / C2 is NULL");
+    if (bil && !a->R3) return fail(RAE_E_INVALID, "R3 is NULL");
+    if (!a->indptr || !a->indices) return fail(RAE_E_INVALID, "indptr / indices is NULL");
+    if (!a->args1 || !a->args2) return fail(RAE_E_INVALID, "args1 / args2 is NULL");
+    if (!a->workspace) return fail(RAE_E_INVALID, "workspace is NULL");
+    if ((uintptr_t)a->workspace & 255) return fail(RAE_E_INVALID, "workspace must be 256-byte aligned");
+    if (a->workspace_bytes < (int64_t)L.total)
+        return fail(RAE_E_INVALID, "workspace_bytes is smaller than rae_relscore_workspace_bytes()");
+    if (v4 && (((uintptr_t)a->W | (uintptr_t)a->Wb | (uintptr_t)a->C1 | (uintptr_t)a->C2 |
+                (uintptr_t)a->R3) & 15))
+        return fail(RAE_E_INVALID, "W / Wb / C1 / C2 / R3 must be 16-byte aligned");
+    if ((r % 4) == 0 && ((uintptr_t)a->A & 15))
+        return fail(RAE_E_INVALID, "A must be 16-byte aligned");
+    if (a->nrows == 0) return RAE_OK;         // nothing is read or written
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)a->workspace;
+    const bool want_joint = out->joint || out->labels_joint;
+    const bool want_fin = want_joint || out->labels_dec;
+    for (int64_t c0 = 0; c0 < a->nrows; c0 += RAE_RS_ROUND) {
+        const int n = (int)std::min<int64_t>(RAE_RS_ROUND, a->nrows - c0);
+        RelArgs k;
+        k.dec = a->decoder; k.m = m; k.r = r;
+        k.A = a->A; k.C1 = a->C1; k.C2 = a->C2; k.R3 = a->R3;
+        k.e1 = a->args1 + a->row0 + c0; k.e2 = a->args2 + a->row0 + c0; k.n_ent = a->n_entities;
+        k.nq = n;
+        k.psi = out->psi ? out->psi + c0 * m : (float*)(ws + L.o_psi);
+        k.ldp = m;
+        if (const int rc = rel_launch(k, st)) return rc;
+        const dim3 ge((unsigned)std::min(ceil_div(n, RAE_RS_EBT / RAE_WAVE), 65536));
+        float* lsm = (float*)(ws + L.o_lsm);
+        if (want_joint) {
+            RelEnc e;
+            e.indptr = a->indptr; e.indices = a->indices; e.values = a->values;
+            e.W = a->W; e.Wb = a->Wb; e.m = m; e.row0 = a->row0 + c0; e.n = n; e.lsm = lsm;
+            hipLaunchKernelGGL(k_rel_enc, ge, dim3(RAE_RS_EBT), 0, st, e);
+        }
+        if (want_fin) {
+            RelFin f;
+            f.psi = k.psi; f.ldp = m; f.lsm = want_joint ? lsm : nullptr; f.Ab = a->Ab;
+            f.e1 = k.e1; f.e2 = k.e2; f.n_ent = a->n_entities; f.m = m; f.n = n;
+            f.joint = out->joint ? out->joint + c0 * m : nullptr;
+            f.labels_dec = out->labels_dec ? out->labels_dec + c0 : nullptr;
+            f.labels_joint = out->labels_joint ? out->labels_joint + c0 : nullptr;
+            hipLaunchKernelGGL(k_rel_fin, ge, dim3(RAE_RS_EBT), 0, st, f);
+        }
+        HIPCHK(hipGetLastError());
     }
     return RAE_OK;
 }

@@ -82,6 +82,7 @@ EXPORTS = (
     "rae_eval_workspace_bytes", "rae_eval_cost",
     "rae_rank_queries", "rae_eval_rank", "rae_rank_workspace_bytes",
     "rae_topk_queries", "rae_eval_topk", "rae_topk_workspace_bytes",
+    "rae_relation_scores", "rae_eval_relations", "rae_relscore_workspace_bytes",
     "rae_cluster_count", "rae_b3_metrics",
     "rae_row_keys", "rae_cluster_key_count", "rae_cluster_topk",
 )
@@ -205,6 +206,33 @@ class RaeTopkOut(C.Structure):
 RAE_ETK_MAXTOP, RAE_ETK_QCHUNK = 32, 1024
 
 
+class RaeRelscoreArgs(C.Structure):
+    """rae_relscore_args (include/rae.h): the decoder's relation scores of caller-given pairs."""
+    _fields_ = [
+        ("decoder", C.c_int32), ("relations", C.c_int32), ("embed", C.c_int32),
+        ("n_entities", C.c_int64), ("A", _P), ("C1", _P), ("C2", _P), ("R3", _P),
+        ("e1", _P), ("e2", _P), ("nq", C.c_int64), ("psi_out", _P), ("ldp", C.c_int64),
+        ("workspace", _P), ("workspace_bytes", C.c_int64),
+    ]
+
+
+class RaeRelOut(C.Structure):
+    """rae_rel_out (include/rae.h): the outputs of rae_eval_relations."""
+    _fields_ = [("psi", _P), ("joint", _P), ("labels_dec", _P), ("labels_joint", _P)]
+
+
+# the relation-score kernel's constants (csrc/rae_relscore.hpp RAE_RS_*): pairs / rows per launch
+# round, K rows per slab, and the examples of one workgroup at `relations`
+RAE_RS_ROUND, RAE_RS_TK = 16384, 32
+
+
+def relscore_block_examples(relations: int) -> int:
+    return 128 if relations <= 16 else 64
+
+
+LABEL_MODES = ("encoder", "decoder", "joint")
+
+
 class RaeError(RuntimeError):
     pass
 
@@ -295,6 +323,13 @@ def load(path: str | None = None):
     lib.rae_topk_workspace_bytes.argtypes = [C.POINTER(RaeTopkArgs), C.POINTER(RaeEvalArgs),
                                              C.c_int32]
     lib.rae_topk_workspace_bytes.restype = C.c_int64
+    lib.rae_relation_scores.argtypes = [C.POINTER(RaeRelscoreArgs), _P]
+    lib.rae_relation_scores.restype = C.c_int
+    lib.rae_eval_relations.argtypes = [C.POINTER(RaeEvalArgs), C.POINTER(RaeRelOut), _P]
+    lib.rae_eval_relations.restype = C.c_int
+    lib.rae_relscore_workspace_bytes.argtypes = [C.POINTER(RaeRelscoreArgs),
+                                                 C.POINTER(RaeEvalArgs)]
+    lib.rae_relscore_workspace_bytes.restype = C.c_int64
     lib.rae_cluster_count.argtypes = [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P]
     lib.rae_cluster_count.restype = C.c_int
     lib.rae_b3_metrics.argtypes = [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P]

@@ -90,6 +90,17 @@ def get_command_args(argv=None, program_name="rae"):
                         "true argument")
     p.add_argument("--predict-top", dest="predict_top", type=int, default=10, metavar="N",
                    help="predictions printed per row and side by --predict-arguments (1..32)")
+    p.add_argument("--predict-relations", dest="predict_relations", type=int, default=0,
+                   metavar="ROWS",
+                   help="after the last epoch print, for the first ROWS rows of the evaluated "
+                        "splits, the two entities, the encoder's label and probability, the "
+                        "--predict-top relations the decoder scores highest for the pair, and "
+                        "the joint label")
+    p.add_argument("--label-with", dest="label_with", choices=["encoder", "decoder", "joint"],
+                   default="encoder",
+                   help="which labels the cluster evaluation and the printed clusters are built "
+                        "from: the encoder's argmax, the decoder's best relation for the two "
+                        "arguments, or the argmax of their joint score")
     p.add_argument("--cluster-eval", dest="cluster_eval", choices=["host", "device"],
                    default="host",
                    help="where the induced clusters are scored: the host evaluator, or the "
@@ -176,7 +187,9 @@ def main(argv=None):
                              eval_rank_ks=args.eval_rank_ks, eval_rank_rows=args.eval_rank_rows,
                              print_preferences=args.print_preferences,
                              predict_arguments=args.predict_arguments,
-                             predict_top=args.predict_top)
+                             predict_top=args.predict_top,
+                             label_with=args.label_with,
+                             predict_relations=args.predict_relations)
     if exchange is not None:
         ind.compile_function()
         rdist.warm_up(exchange, ind.engine.exchange_buf)

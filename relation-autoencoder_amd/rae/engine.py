@@ -1128,6 +1128,141 @@ class TrainEngine:
         ents, scores = self.topk_entities(Q, top)
         return ents.reshape(2, self.m, top), scores.reshape(2, self.m, top)
 
+    # ------------------------------------------------------------------ relation scores
+    label_with = "encoder"           # which labels the cluster evaluation / profiles count
+
+    def _rel_eval_args(self, split: DeviceSplit, row0: int, nrows: int):
+        """rae_eval_args of rae_eval_relations with the engine's workspace (once per engine)."""
+        named = self._named
+        R3 = named.get("R", named.get("C"))
+        a = _lib.RaeEvalArgs()
+        a.decoder = self.cfg.decoder
+        a.relations, a.embed = self.m, self.r
+        a.n_entities = self.cfg.n_entities
+        a.alpha = self.cfg.alpha
+        p = _lib.ptr
+        a.W, a.Wb, a.A, a.Ab = p(named["W"]), p(named["Wb"]), p(named["A"]), p(named["Ab"])
+        a.C1, a.C2, a.R3 = p(named.get("C1")), p(named.get("C2")), p(R3)
+        a.indptr, a.indices, a.values = p(split.indptr), p(split.indices), p(split.values)
+        a.args1, a.args2 = p(split.args1), p(split.args2)
+        a.row0, a.nrows = int(row0), int(nrows)
+        if getattr(self, "_rel_ws", None) is None:
+            need = int(self.lib.rae_relscore_workspace_bytes(None, C.byref(a)))
+            if need < 0:
+                _lib.check(-1, "rae_relscore_workspace_bytes")
+            self._rel_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+        a.workspace, a.workspace_bytes = p(self._rel_ws), int(self._rel_ws.numel())
+        return a
+
+    def relation_scores(self, e1, e2):
+        """psi ((nq, m) fp32): the decoder's score of every relation for the entity pairs
+        (e1[q], e2[q]) at the current parameters (rae_relation_scores; include/rae.h has the
+        definition per decoder).  Ids outside [0, n_entities) raise IndexError on the host.
+        Queued on the current stream.  Touches no training state; partitioned update with stale
+        rows: gathers the parameters first (a collective, like cluster_metrics)."""
+        if self.stale(accumulators=False):
+            self.sync_replicas(accumulators=False)
+        ids = []
+        for e in (e1, e2):
+            h = np.ascontiguousarray(e.cpu().numpy() if torch.is_tensor(e) else e).reshape(-1)
+            if h.size and (h.min() < 0 or h.max() >= self.cfg.n_entities):
+                raise IndexError(f"entity ids must be in [0, {self.cfg.n_entities})")
+            ids.append(torch.as_tensor(h.astype(np.int32), device=self.device))
+        if ids[0].numel() != ids[1].numel():
+            raise ValueError("e1 and e2 differ in length")
+        nq = int(ids[0].numel())
+        key = ("psi", nq)
+        bufs = self.__dict__.setdefault("_rel_bufs", {})
+        if key not in bufs:                  # once per shape
+            bufs[key] = torch.empty((nq, self.m), dtype=torch.float32, device=self.device)
+        psi = bufs[key]
+        named = self._named
+        p = _lib.ptr
+        a = _lib.RaeRelscoreArgs()
+        a.decoder, a.relations, a.embed = self.cfg.decoder, self.m, self.r
+        a.n_entities = self.cfg.n_entities
+        a.A, a.C1, a.C2 = p(named["A"]), p(named.get("C1")), p(named.get("C2"))
+        a.R3 = p(named.get("R", named.get("C")))
+        a.e1, a.e2, a.nq = p(ids[0]), p(ids[1]), nq
+        a.psi_out, a.ldp = p(psi), self.m
+        _lib.check(self.lib.rae_relation_scores(C.byref(a), self._stream()), "rae_relation_scores")
+        self._rel_keep = ids                 # the id arrays live until the next call
+        return psi
+
+    def top_relations(self, e1, e2, top: int = 5):
+        """(psi, values, relations): relation_scores and its `top` largest columns per pair
+        (torch.topk: m <= 512 needs no kernel)."""
+        psi = self.relation_scores(e1, e2)
+        vals, rel = torch.topk(psi, min(int(top), self.m), dim=1)
+        return psi, vals, rel
+
+    def queue_label_relations(self, split: DeviceSplit, row0: int, nrows: int, mode: str,
+                              labels=None):
+        """Queue the labels of rows [row0, row0+nrows) of `split` under `mode` on the current
+        stream (no host synchronisation) into `labels` (default: the engine's label buffer
+        self._cl_labels, allocated once per shape): 'encoder' is rae_label, 'decoder' / 'joint'
+        are rae_eval_relations' argmax of psi / of the joint score."""
+        if mode not in _lib.LABEL_MODES:
+            raise ValueError(f"mode must be one of {_lib.LABEL_MODES}")
+        row0, nrows = int(row0), int(nrows)
+        if row0 < 0 or nrows < 0 or row0 + nrows > split.N:
+            raise IndexError(f"rows [{row0}, {row0 + nrows}) out of the split's {split.N}")
+        if labels is None:
+            if getattr(self, "_cl_labels", None) is None or self._cl_labels.numel() < nrows:
+                self._cl_labels = torch.empty(max(nrows, 1), dtype=torch.int64,
+                                              device=self.device)
+            labels = self._cl_labels
+        st = self._stream()
+        if mode == "encoder":
+            W, Wb = self.model.params[0], self.model.params[1]
+            _lib.check(self.lib.rae_label(
+                C.c_void_p(split.indptr.data_ptr()), C.c_void_p(split.indices.data_ptr()),
+                C.c_void_p(split.values.data_ptr()) if split.values is not None else None,
+                C.c_void_p(W.data_ptr()), C.c_void_p(Wb.data_ptr()), self.m, row0, nrows,
+                C.c_void_p(labels.data_ptr()), None, st), "rae_label")
+            return labels
+        a = self._rel_eval_args(split, row0, nrows)
+        o = _lib.RaeRelOut()
+        if mode == "decoder":
+            o.labels_dec = labels.data_ptr()
+        else:
+            o.labels_joint = labels.data_ptr()
+        _lib.check(self.lib.rae_eval_relations(C.byref(a), C.byref(o), st), "rae_eval_relations")
+        return labels
+
+    def label_relations(self, split: DeviceSplit, row0: int = 0, nrows: int | None = None,
+                        mode: str = "joint"):
+        """Labels (int64 tensor) of rows [row0, row0+nrows) of `split` under `mode` in
+        encoder | decoder | joint.  Touches no training state; partitioned update with stale
+        rows: gathers the parameters first (a collective, like cluster_metrics)."""
+        if self.stale(accumulators=False):
+            self.sync_replicas(accumulators=False)
+        row0 = int(row0)
+        nrows = split.N - row0 if nrows is None else int(nrows)
+        out = torch.empty(max(nrows, 1), dtype=torch.int64, device=self.device)
+        self.queue_label_relations(split, row0, nrows, mode, out)
+        return out[:nrows]
+
+    def eval_relations(self, split: DeviceSplit, row0: int = 0, nrows: int | None = None):
+        """(psi, joint, labels_dec, labels_joint) of rows [row0, row0+nrows) of `split`
+        (rae_eval_relations, every output).  Touches no training state."""
+        if self.stale(accumulators=False):
+            self.sync_replicas(accumulators=False)
+        row0 = int(row0)
+        nrows = split.N - row0 if nrows is None else int(nrows)
+        if row0 < 0 or nrows < 0 or row0 + nrows > split.N:
+            raise IndexError(f"rows [{row0}, {row0 + nrows}) out of the split's {split.N}")
+        mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)
+        psi, joint = mk((nrows, self.m), torch.float32), mk((nrows, self.m), torch.float32)
+        ld, lj = mk(max(nrows, 1), torch.int64), mk(max(nrows, 1), torch.int64)
+        a = self._rel_eval_args(split, row0, nrows)
+        o = _lib.RaeRelOut()
+        o.psi, o.joint = psi.data_ptr(), joint.data_ptr()
+        o.labels_dec, o.labels_joint = ld.data_ptr(), lj.data_ptr()
+        _lib.check(self.lib.rae_eval_relations(C.byref(a), C.byref(o), self._stream()),
+                   "rae_eval_relations")
+        return psi, joint, ld[:nrows], lj[:nrows]
+
     # ------------------------------------------------------------------ cluster evaluation
     def _gold_dev(self, split: DeviceSplit, gold_index):
         """The gold ids (int32, split.N; -1 past the index's rows) and sizes (int64) of
@@ -1176,11 +1311,14 @@ class TrainEngine:
         st = self._stream()
         W, Wb = self.model.params[0], self.model.params[1]
         lab = self._cl_labels
-        _lib.check(self.lib.rae_label(
-            C.c_void_p(split.indptr.data_ptr()), C.c_void_p(split.indices.data_ptr()),
-            C.c_void_p(split.values.data_ptr()) if split.values is not None else None,
-            C.c_void_p(W.data_ptr()), C.c_void_p(Wb.data_ptr()), self.m, row0, nrows,
-            C.c_void_p(lab.data_ptr()), None, st), "rae_label")
+        if self.label_with != "encoder":     # the same buffer, from rae_eval_relations
+            self.queue_label_relations(split, row0, nrows, self.label_with, lab)
+        else:
+            _lib.check(self.lib.rae_label(
+                C.c_void_p(split.indptr.data_ptr()), C.c_void_p(split.indices.data_ptr()),
+                C.c_void_p(split.values.data_ptr()) if split.values is not None else None,
+                C.c_void_p(W.data_ptr()), C.c_void_p(Wb.data_ptr()), self.m, row0, nrows,
+                C.c_void_p(lab.data_ptr()), None, st), "rae_label")
         self._cl_labels_of = (id(split), row0, nrows)    # queue_cluster_profiles(reuse_labels)
         _lib.check(self.lib.rae_cluster_count(
             C.c_void_p(lab.data_ptr()), C.c_void_p(ids_d.data_ptr() + 4 * row0), nrows, self.m,
@@ -1283,11 +1421,14 @@ class TrainEngine:
                 self._cl_labels = torch.empty(max(nrows, 1), dtype=torch.int64,
                                               device=self.device)
             W, Wb = self.model.params[0], self.model.params[1]
-            _lib.check(self.lib.rae_label(
-                C.c_void_p(split.indptr.data_ptr()), C.c_void_p(split.indices.data_ptr()),
-                C.c_void_p(split.values.data_ptr()) if split.values is not None else None,
-                C.c_void_p(W.data_ptr()), C.c_void_p(Wb.data_ptr()), self.m, row0, nrows,
-                C.c_void_p(self._cl_labels.data_ptr()), None, st), "rae_label")
+            if self.label_with != "encoder":
+                self.queue_label_relations(split, row0, nrows, self.label_with, self._cl_labels)
+            else:
+                _lib.check(self.lib.rae_label(
+                    C.c_void_p(split.indptr.data_ptr()), C.c_void_p(split.indices.data_ptr()),
+                    C.c_void_p(split.values.data_ptr()) if split.values is not None else None,
+                    C.c_void_p(W.data_ptr()), C.c_void_p(Wb.data_ptr()), self.m, row0, nrows,
+                    C.c_void_p(self._cl_labels.data_ptr()), None, st), "rae_label")
         self._cl_labels_of = None
         _lib.check(self.lib.rae_cluster_key_count(
             C.c_void_p(self._cl_labels.data_ptr()), C.c_void_p(keys_d.data_ptr() + 4 * row0),

@@ -386,6 +386,72 @@ def format_relation_preferences(ents, scores, names=None):
     return lines
 
 
+# ------------------------------------------------------------------ relation scores from the decoder
+def relation_scores(params, decoder, e1, e2):
+    """psi (nq, m) float64, the oracle of rae_relation_scores: the decoder's score of every
+    relation k for the pairs (e1[q], e2[q]), a1 = A[e1], a2 = A[e2]:
+        sp          <C1[:,k], a1> + <C2[:,k], a1>     (A[args1] twice, as the objective scores it)
+        rescal      a1^T R[:,:,k] a2
+        rescal+sp   a1^T C[:,:,k] a2 + <C1[:,k], a1> + <C2[:,k], a2>
+    params: name -> array (A (n, r); C1, C2 (r, m); R or C (r, r, m)).  Ids out of range raise
+    IndexError."""
+    if decoder not in ("sp", "rescal", "rescal+sp"):
+        raise ValueError(f"unknown decoder {decoder!r}")
+    A = np.asarray(params["A"], dtype=np.float64)
+    e1 = np.asarray(e1).astype(np.int64).reshape(-1)
+    e2 = np.asarray(e2).astype(np.int64).reshape(-1)
+    for e in (e1, e2):
+        if e.size and (e.min() < 0 or e.max() >= A.shape[0]):
+            raise IndexError(f"entity ids must be in [0, {A.shape[0]})")
+    a1, a2 = A[e1], A[e2]
+    if decoder == "sp":
+        return a1 @ np.asarray(params["C1"], np.float64) + a1 @ np.asarray(params["C2"], np.float64)
+    R = np.asarray(params["R" if decoder == "rescal" else "C"], dtype=np.float64)
+    psi = np.einsum("bi,ijk,bj->bk", a1, R, a2, optimize=True)
+    if decoder == "rescal+sp":
+        psi = psi + a1 @ np.asarray(params["C1"], np.float64) \
+            + a2 @ np.asarray(params["C2"], np.float64)
+    return psi
+
+
+def log_sigmoid(x):
+    """log(sigmoid(x)) = -softplus(-x), float64, stable."""
+    x = np.asarray(x, dtype=np.float64)
+    return -(np.maximum(-x, 0.0) + np.log1p(np.exp(-np.abs(x))))
+
+
+def joint_scores(logits, psi, Ab, e1, e2):
+    """J (nrows, m) float64, the oracle of rae_eval_relations' joint output:
+    J_k = logsoftmax_k(logits) + logsig(psi_k + Ab[e1]) + logsig(psi_k + Ab[e2]), the
+    log-softmax as z_k - log sum exp z with z = logits - max logits."""
+    S = np.asarray(logits, dtype=np.float64)
+    psi = np.asarray(psi, dtype=np.float64)
+    Ab = np.asarray(Ab, dtype=np.float64).reshape(-1)
+    z = S - S.max(axis=1, keepdims=True)
+    lsm = z - np.log(np.exp(z).sum(axis=1, keepdims=True))
+    b1 = Ab[np.asarray(e1).astype(np.int64)][:, None]
+    b2 = Ab[np.asarray(e2).astype(np.int64)][:, None]
+    return lsm + log_sigmoid(psi + b1) + log_sigmoid(psi + b2)
+
+
+def format_relation_predictions(e1, e2, enc_labels, enc_probs, psi, joint_labels, top,
+                                names=None, row0=0):
+    """One line per row, tab-separated: 'relations', the row, the two entities, the encoder's
+    label as k:probability, the `top` relations by psi as k:psi (best first, ties by relation
+    ascending), then 'joint' and the joint label."""
+    psi = np.asarray(psi)
+    lines = []
+    for b in range(psi.shape[0]):
+        row = psi[b]
+        order = np.lexsort((np.arange(row.shape[0]), -row))[:int(top)]
+        lines.append("\t".join(
+            ["relations", str(row0 + b), entity_name(names, e1[b]), entity_name(names, e2[b]),
+             "{}:{:.9g}".format(int(enc_labels[b]), float(enc_probs[b]))] +
+            ["{}:{:.9g}".format(int(k), float(row[k])) for k in order] +
+            ["joint", str(int(joint_labels[b]))]))
+    return lines
+
+
 def format_argument_predictions(ents, scores, true, names=None, row0=0):
     """ents / scores (nrows, 2, top) of TrainEngine.predict_arguments, true (nrows, 2) the rows'
     arguments -> one line per row and side, tab-separated: 'predictions', the row, the side (1 or

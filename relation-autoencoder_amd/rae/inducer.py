@@ -15,7 +15,7 @@ from .data import SPLIT_LABELS
 from .engine import DeviceSplit, TrainEngine
 from .evaluation import (GoldIndex, KeyIndex, construct_split_evaluator,
                          format_argument_predictions, format_cluster_profiles,
-                         format_relation_preferences, key_table, row_keys, topk_from_table)
+                         format_relation_predictions, format_relation_preferences, key_table, row_keys, topk_from_table)
 from .model import OieModelFunctions, _as_bool, make_optimizer
 from .negatives import NegativeExampleGenerator
 
@@ -78,7 +78,12 @@ class ReconstructInducer:
                  index_overlap=True, p2p_cross_device=False, p2p_timeout=5.0,
                  eval_cost=False, eval_seed=None, cluster_eval="host", print_clusters="off",
                  print_top=5, print_by="trigger", eval_rank=False, eval_rank_ks=(1, 10, 100),
-                 eval_rank_rows=None, print_preferences=0, predict_arguments=0, predict_top=10):
+                 eval_rank_rows=None, print_preferences=0, predict_arguments=0, predict_top=10,
+                 label_with="encoder", predict_relations=0):
+        if label_with not in ("encoder", "decoder", "joint"):
+            raise ValueError("label_with must be 'encoder', 'decoder' or 'joint'")
+        if int(predict_relations) < 0:
+            raise ValueError("predict_relations must be >= 0")
         if not 0 <= int(print_preferences) <= 32:
             raise ValueError("print_preferences must be in [0, 32] (0: off)")
         if int(predict_arguments) < 0 or not 1 <= int(predict_top) <= 32:
@@ -157,6 +162,15 @@ class ReconstructInducer:
         self.print_preferences = int(print_preferences)
         self.predict_arguments = int(predict_arguments)
         self.predict_top = int(predict_top)
+        # label_with: which labels _labels, get_clusters_sets, the host and device cluster
+        # evaluation and the cluster profiles use -- "encoder": argmax of the encoder's logits
+        # (rae_label, the reference's); "decoder": the relation the two arguments themselves
+        # score highest (argmax psi); "joint": argmax of logsoftmax + l (rae_eval_relations).
+        # predict_relations: after the last epoch, per row of the first ROWS rows of the
+        # evaluated splits, the encoder's label, the predict_top relations by psi and the joint
+        # label (TrainEngine.eval_relations)
+        self.label_with = label_with
+        self.predict_relations = int(predict_relations)
         # cluster_eval: where learn() scores the induced clusters -- "host": the label download
         # and the Python sets of the reference (get_clusters_sets + SingleLabelClusterEvaluation);
         # "device": the contingency table and B^3 on the GPU (TrainEngine.cluster_metrics), same
@@ -243,6 +257,7 @@ class ReconstructInducer:
                                   p2p_cross_device=self.p2p_cross_device,
                                   p2p_timeout=self.p2p_timeout)
         self.func["train"] = _TrainFunction(self.engine)
+        self.engine.label_with = self.label_with
         self.engine.eval_sampler = self.negativeSampler      # its CDF only (eval_negatives)
         self._dev_split = {}
         for key in self.data.generate_split_keys():
@@ -344,6 +359,11 @@ class ReconstructInducer:
                 lines = self.argument_prediction_lines(split)
                 if verbose:
                     print("\n".join(lines))
+        if self.predict_relations:
+            for split in (SPLIT_LABELS[:1] if self._mode() == 1 else SPLIT_LABELS[1:]):
+                lines = self.relation_prediction_lines(split)
+                if verbose:
+                    print("\n".join(lines))
         return self.train_errors
 
     def relation_preference_lines(self):
@@ -366,6 +386,25 @@ class ReconstructInducer:
         true = np.stack([np.asarray(sp.args1[:nrows]), np.asarray(sp.args2[:nrows])], axis=1)
         return ["{} predictions ({} rows)".format(split, nrows)] + format_argument_predictions(
             ents.cpu().numpy(), scores.cpu().numpy(), true, getattr(self.data, "id2Arg", None))
+
+    def relation_prediction_lines(self, split):
+        """predict_relations' lines for the first predict_relations rows of `split`: a header,
+        then one line per row (rae.evaluation.format_relation_predictions)."""
+        if not self._check_for_compiled_functions():
+            self.compile_function()
+        ds = self._dev_split[split]
+        nrows = max(0, min(ds.N, self.predict_relations))
+        head = "{} relations ({} rows)".format(split, nrows)
+        if nrows == 0:
+            return [head]
+        lab, pr = self.engine.label(ds, 0, nrows)
+        psi, _, _, lj = self.engine.eval_relations(ds, 0, nrows)
+        lab, pr = lab.cpu().numpy(), pr.cpu().numpy()
+        sp = self.data.split[split]
+        return [head] + format_relation_predictions(
+            np.asarray(sp.args1[:nrows]), np.asarray(sp.args2[:nrows]), lab,
+            pr[np.arange(nrows), lab], psi.cpu().numpy(), lj.cpu().numpy(),
+            min(self.predict_top, self.relationNum), getattr(self.data, "id2Arg", None))
 
     def evaluate_cost(self, split, verbose=True):
         """The forward-only objective of the whole `split` at the current parameters, against
@@ -399,6 +438,11 @@ class ReconstructInducer:
     # ------------------------------------------------------------------ clusters / eval
     def _labels(self, split):
         nbs = self.data.split[split].args1.shape[0] // self.batch_size
+        if self.label_with != "encoder":
+            if not self._check_for_compiled_functions():
+                self.compile_function()
+            return self.engine.label_relations(self._dev_split[split], 0, nbs * self.batch_size,
+                                               self.label_with).cpu().numpy()
         return self.func["label_" + split].all_labels(nbs)
 
     def get_clusters_sets(self, split):
