@@ -1476,110 +1476,195 @@ extern "C" int rae_label(const int32_t* indptr, const int32_t* indices, const fl
     return RAE_OK;
 }
 
-// ---- forward-only objective -----------------------------------------------------------------
+// ---- plan-free evaluation: the argument checks, workspace blocks and launch prelude that
+// ---- rae_eval_cost / _rank / _topk / _relations share (host only) -----------------------------
 namespace {
-struct EvalLayout {
-    int64_t chunk;                           // examples per launch round
-    size_t o_partial, o_terms, o_P, o_v, o_w, total;
-};
 inline size_t ev_align(size_t x) { return (x + 255) & ~(size_t)255; }
-// argument check (host only) and the workspace layout
-// the shape limits of the evaluation kernels (rae_eval_cost, rae_eval_rank)
-int eval_shapes(const rae_eval_args* a, bool need_s) {
-    if (!a) return fail(RAE_E_INVALID, "null argument");
-    if (a->decoder < 0 || a->decoder > 2) return fail(RAE_E_INVALID, "decoder must be 0..2");
-    const int m = a->relations, r = a->embed, s = a->neg_samples;
+
+int entity_count(int64_t n) {
+    if (n < 1 || n >= (1ll << 31)) return fail(RAE_E_INVALID, "n_entities must be in [1, 2^31)");
+    return RAE_OK;
+}
+// shapes of the caller-given-queries entries (rae_rank_queries, rae_topk_queries)
+int query_shapes(int embed, int64_t n_entities) {
+    if (embed < 1 || embed > 1024) return fail(RAE_E_INVALID, "embed must be in [1, 1024]");
+    return entity_count(n_entities);
+}
+// the shape limits of the evaluation kernels, in two halves (eval_shapes checks neg_samples
+// between them)
+int model_shapes(int dec, int m, int r) {
+    if (dec < 0 || dec > 2) return fail(RAE_E_INVALID, "decoder must be 0..2");
     if (m < 1 || m > 512) return fail(RAE_E_INVALID, "relations must be in [1, 512]");
     if ((m % 4) != 0 && m > 128)
         return fail(RAE_E_INVALID, "relations must be a multiple of 4 above 128");
     if (r < 1 || r > 1024) return fail(RAE_E_INVALID, "embed must be in [1, 1024]");
-    if (need_s && s < 1) return fail(RAE_E_INVALID, "neg_samples must be >= 1");
-    const bool bil = a->decoder != RAE_DEC_SP;
-    if (bil && eval_mt_lds_bytes(m) > 160 * 1024)
+    return RAE_OK;
+}
+int bilinear_shapes(int dec, int m) {
+    if (dec != RAE_DEC_SP && eval_mt_lds_bytes(m) > 160 * 1024)
         return fail(RAE_E_INVALID, "relations must be <= 320 for the bilinear decoders");
-    if (eval_dec_lds_floats(a->decoder, m, r) * 4 > 160 * 1024)
+    return RAE_OK;
+}
+int eval_shapes(const rae_eval_args* a, bool need_s) {
+    if (!a) return fail(RAE_E_INVALID, "null argument");
+    if (const int rc = model_shapes(a->decoder, a->relations, a->embed)) return rc;
+    if (need_s && a->neg_samples < 1) return fail(RAE_E_INVALID, "neg_samples must be >= 1");
+    if (const int rc = bilinear_shapes(a->decoder, a->relations)) return rc;
+    if (eval_dec_lds_floats(a->decoder, a->relations, a->embed) * 4 > 160 * 1024)
         return fail(RAE_E_INVALID, "relations / embed need more than 160 KiB of LDS per tile");
     return RAE_OK;
 }
-int eval_check(const rae_eval_args* a, EvalLayout& L, bool need_buffers) {
-    if (const int rc = eval_shapes(a, true)) return rc;
-    const int m = a->relations, r = a->embed;
-    const bool bil = a->decoder != RAE_DEC_SP;
-    L.chunk = bil ? RAE_EV_CHUNK_BIL : RAE_EV_CHUNK_SP;
-    const size_t ch = (size_t)L.chunk, r4 = (size_t)eval_r4(r);
-    size_t o = 0;
-    L.o_partial = o; o = ev_align(o + (ch / RAE_EV_SUMROWS) * 3 * sizeof(double));
-    L.o_terms = o;   o = ev_align(o + ch * 3 * sizeof(float));
-    L.o_P = o;       if (bil) o = ev_align(o + ch * m * sizeof(float));
-    L.o_v = o;       if (bil) o = ev_align(o + (size_t)eval_nbj(r) * ch * r4 * sizeof(float));
-    L.o_w = o;       if (bil) o = ev_align(o + (size_t)eval_nbi(r) * ch * r4 * sizeof(float));
-    L.total = o;
-    if (!need_buffers) return RAE_OK;
-    if (a->n_entities < 1 || a->n_entities >= (1ll << 31))
-        return fail(RAE_E_INVALID, "n_entities must be in [1, 2^31)");
+// the shapes of the relation-score kernel: the same limits without the tile's
+int rel_shapes(int dec, int m, int r, int64_t n_entities) {
+    if (const int rc = model_shapes(dec, m, r)) return rc;
+    if (const int rc = bilinear_shapes(dec, m)) return rc;
+    return entity_count(n_entities);
+}
+
+// the buffer check of the four entries, in blocks: each entry calls them in this order with its
+// own outputs' checks between them
+int check_rows(const rae_eval_args* a) {
     if (a->nrows < 0) return fail(RAE_E_INVALID, "nrows must be >= 0");
     if (a->row0 < 0 || a->row0 + a->nrows >= (1ll << 31))
         return fail(RAE_E_INVALID, "row0 / nrows out of range");
+    return RAE_OK;
+}
+int check_model(const rae_eval_args* a) {
     if (!a->W) return fail(RAE_E_INVALID, "W is NULL");
     if (!a->Wb) return fail(RAE_E_INVALID, "Wb is NULL");
     if (!a->A) return fail(RAE_E_INVALID, "A is NULL");
     if (!a->Ab) return fail(RAE_E_INVALID, "Ab is NULL");
     if (a->decoder != RAE_DEC_RESCAL && (!a->C1 || !a->C2))
         return fail(RAE_E_INVALID, "C1 / C2 is NULL");
-    if (bil && !a->R3) return fail(RAE_E_INVALID, "R3 is NULL");
+    if (a->decoder != RAE_DEC_SP && !a->R3) return fail(RAE_E_INVALID, "R3 is NULL");
     if (!a->indptr || !a->indices) return fail(RAE_E_INVALID, "indptr / indices is NULL");
     if (!a->args1 || !a->args2) return fail(RAE_E_INVALID, "args1 / args2 is NULL");
-    if (!a->neg1 || !a->neg2) return fail(RAE_E_INVALID, "neg1 / neg2 is NULL");
-    if (a->neg_stride < a->row0 + a->nrows)
-        return fail(RAE_E_INVALID, "neg_stride is smaller than row0 + nrows");
-    if (!a->sums_out) return fail(RAE_E_INVALID, "sums_out is NULL");
-    if (!a->workspace) return fail(RAE_E_INVALID, "workspace is NULL");
-    if ((uintptr_t)a->workspace & 255) return fail(RAE_E_INVALID, "workspace must be 256-byte aligned");
-    if (a->workspace_bytes < (int64_t)L.total)
-        return fail(RAE_E_INVALID, "workspace_bytes is smaller than rae_eval_workspace_bytes()");
-    if ((m % 4) == 0 && (((uintptr_t)a->W | (uintptr_t)a->Wb | (uintptr_t)a->C1 |
-                          (uintptr_t)a->C2 | (uintptr_t)a->R3) & 15))
+    return RAE_OK;
+}
+int check_workspace(const void* ws, int64_t bytes, size_t need, const char* sizer) {
+    if (!ws) return fail(RAE_E_INVALID, "workspace is NULL");
+    if ((uintptr_t)ws & 255) return fail(RAE_E_INVALID, "workspace must be 256-byte aligned");
+    if (bytes < (int64_t)need)
+        return fail(RAE_E_INVALID, std::string("workspace_bytes is smaller than ") + sizer + "()");
+    return RAE_OK;
+}
+int check_align(const rae_eval_args* a) {
+    if ((a->relations % 4) == 0 && (((uintptr_t)a->W | (uintptr_t)a->Wb | (uintptr_t)a->C1 |
+                                     (uintptr_t)a->C2 | (uintptr_t)a->R3) & 15))
         return fail(RAE_E_INVALID, "W / Wb / C1 / C2 / R3 must be 16-byte aligned");
-    if ((r % 4) == 0 && ((uintptr_t)a->A & 15))
+    if ((a->embed % 4) == 0 && ((uintptr_t)a->A & 15))
         return fail(RAE_E_INVALID, "A must be 16-byte aligned");
+    return RAE_OK;
+}
+
+// workspace blocks, laid from offset o on; each returns the offset past its block
+struct EncWs { size_t o_terms, o_P, o_v, o_w; };      // the encoder prelude's, of ch examples
+struct QueryWs { size_t o_Q, o_c, o_u, o_skip; };     // the 2 ch queries k_rank_build writes
+size_t lay_enc(const rae_eval_args* a, size_t ch, size_t o, EncWs& L) {
+    const bool bil = a->decoder != RAE_DEC_SP;
+    const size_t m = (size_t)a->relations, r4 = (size_t)eval_r4(a->embed);
+    L.o_terms = o;   o = ev_align(o + ch * 3 * sizeof(float));
+    L.o_P = o;       if (bil) o = ev_align(o + ch * m * sizeof(float));
+    L.o_v = o;       if (bil) o = ev_align(o + (size_t)eval_nbj(a->embed) * ch * r4 * sizeof(float));
+    L.o_w = o;       if (bil) o = ev_align(o + (size_t)eval_nbi(a->embed) * ch * r4 * sizeof(float));
+    return o;
+}
+size_t lay_queries(const rae_eval_args* a, size_t ch, size_t o, QueryWs& L) {
+    L.o_Q = o;       o = ev_align(o + 2 * ch * (size_t)eval_r4(a->embed) * sizeof(float));
+    L.o_c = o;       o = ev_align(o + 2 * ch * sizeof(float));
+    L.o_u = o;       o = ev_align(o + 2 * ch * sizeof(float));
+    L.o_skip = o;    o = ev_align(o + 2 * ch * sizeof(int32_t));
+    return o;
+}
+
+// the kernels' arguments of chunks of cap examples, without negatives (rae_eval_cost adds them);
+// row0 and n are the chunk's
+EvalArgs eval_args_of(const rae_eval_args* a, int cap, const EncWs& L) {
+    char* ws = (char*)a->workspace;
+    EvalArgs e;
+    e.dec = a->decoder; e.m = a->relations; e.r = a->embed; e.s = 0; e.alpha = a->alpha;
+    e.W = a->W; e.Wb = a->Wb; e.A = a->A; e.Ab = a->Ab; e.C1 = a->C1; e.C2 = a->C2; e.R3 = a->R3;
+    e.indptr = a->indptr; e.indices = a->indices; e.values = a->values;
+    e.args1 = a->args1; e.args2 = a->args2; e.neg1 = nullptr; e.neg2 = nullptr;
+    e.neg_stride = 0;
+    e.cap = cap; e.r4 = eval_r4(a->embed);
+    e.terms = (float*)(ws + L.o_terms);
+    e.P = (float*)(ws + L.o_P); e.vpart = (float*)(ws + L.o_v); e.wpart = (float*)(ws + L.o_w);
+    return e;
+}
+// large dynamic LDS is opted into per kernel (not a stream operation): the decoder-side kernel
+// of the entry and k_eval_mt
+int eval_large_lds(const void* dec_kernel, const rae_eval_args* a) {
+    const size_t lds_dec = eval_dec_lds_floats(a->decoder, a->relations, a->embed) * 4;
+    const size_t lds_mt = eval_mt_lds_bytes(a->relations);
+    const bool v4 = (a->relations % 4) == 0;
+    if (lds_dec > 48 * 1024)
+        HIPCHK(hipFuncSetAttribute(dec_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)lds_dec));
+    if (a->decoder != RAE_DEC_SP && lds_mt > 48 * 1024)
+        HIPCHK(hipFuncSetAttribute(v4 ? (const void*)k_eval_mt<true> : (const void*)k_eval_mt<false>,
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_mt));
+    return RAE_OK;
+}
+// the bilinear decoders' prelude of one chunk: P and the partials of M a2 / M^T a1
+void launch_enc_mt(const EvalArgs& e, hipStream_t st) {
+    if (e.dec == RAE_DEC_SP) return;
+    const dim3 ge((unsigned)std::min(ceil_div(e.n, RAE_EV_NW), 65536));
+    const dim3 gm((unsigned)(eval_nbi(e.r) * eval_nbj(e.r)));
+    with_bool((e.m % 4) == 0, [&](auto V) {
+        hipLaunchKernelGGL(k_eval_enc<RAE_CV(V)>, ge, dim3(RAE_EV_BT), 0, st, e);
+        hipLaunchKernelGGL(k_eval_mt<RAE_CV(V)>, gm, dim3(RAE_EV_MTT), eval_mt_lds_bytes(e.m), st, e);
+    });
+}
+}  // namespace
+
+// ---- forward-only objective -----------------------------------------------------------------
+namespace {
+struct EvalLayout {
+    int64_t chunk;                           // examples per launch round
+    size_t o_partial, total;
+    EncWs enc;
+};
+int eval_layout(const rae_eval_args* a, EvalLayout& L) {
+    if (const int rc = eval_shapes(a, true)) return rc;
+    L.chunk = a->decoder != RAE_DEC_SP ? RAE_EV_CHUNK_BIL : RAE_EV_CHUNK_SP;
+    const size_t ch = (size_t)L.chunk;
+    L.o_partial = 0;
+    L.total = lay_enc(a, ch, ev_align((ch / RAE_EV_SUMROWS) * 3 * sizeof(double)), L.enc);
     return RAE_OK;
 }
 }  // namespace
 
 extern "C" int64_t rae_eval_workspace_bytes(const rae_eval_args* a) {
     EvalLayout L;
-    if (eval_check(a, L, false)) return -1;
+    if (eval_layout(a, L)) return -1;
     return (int64_t)L.total;
 }
 
 extern "C" int rae_eval_cost(const rae_eval_args* a, rae_stream_t stream) {
     EvalLayout L;
-    const int rc = eval_check(a, L, true);
-    if (rc) return rc;
+    if (const int rc = eval_layout(a, L)) return rc;
+    if (const int rc = entity_count(a->n_entities)) return rc;
+    if (const int rc = check_rows(a)) return rc;
+    if (const int rc = check_model(a)) return rc;
+    if (!a->neg1 || !a->neg2) return fail(RAE_E_INVALID, "neg1 / neg2 is NULL");
+    if (a->neg_stride < a->row0 + a->nrows)
+        return fail(RAE_E_INVALID, "neg_stride is smaller than row0 + nrows");
+    if (!a->sums_out) return fail(RAE_E_INVALID, "sums_out is NULL");
+    if (const int rc = check_workspace(a->workspace, a->workspace_bytes, L.total,
+                                       "rae_eval_workspace_bytes"))
+        return rc;
+    if (const int rc = check_align(a)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const int m = a->relations, r = a->embed;
-    const bool bil = a->decoder != RAE_DEC_SP, v4 = (m % 4) == 0;
-    char* ws = (char*)a->workspace;
-    double* partial = (double*)(ws + L.o_partial);
-    const size_t lds_dec = eval_dec_lds_floats(a->decoder, m, r) * 4;
-    const size_t lds_mt = eval_mt_lds_bytes(m);
-    // large dynamic LDS is opted into per kernel (not a stream operation)
-    if (lds_dec > 48 * 1024) {
-        HIPCHK(hipFuncSetAttribute(v4 ? (const void*)k_eval_dec<true> : (const void*)k_eval_dec<false>,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_dec));
-    }
-    if (bil && lds_mt > 48 * 1024) {
-        HIPCHK(hipFuncSetAttribute(v4 ? (const void*)k_eval_mt<true> : (const void*)k_eval_mt<false>,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_mt));
-    }
-    EvalArgs e;
-    e.dec = a->decoder; e.m = m; e.r = r; e.s = a->neg_samples; e.alpha = a->alpha;
-    e.W = a->W; e.Wb = a->Wb; e.A = a->A; e.Ab = a->Ab; e.C1 = a->C1; e.C2 = a->C2; e.R3 = a->R3;
-    e.indptr = a->indptr; e.indices = a->indices; e.values = a->values;
-    e.args1 = a->args1; e.args2 = a->args2; e.neg1 = a->neg1; e.neg2 = a->neg2;
-    e.neg_stride = a->neg_stride;
-    e.cap = (int)L.chunk; e.r4 = eval_r4(r);
-    e.P = (float*)(ws + L.o_P); e.vpart = (float*)(ws + L.o_v); e.wpart = (float*)(ws + L.o_w);
+    const bool v4 = (a->relations % 4) == 0;
+    double* partial = (double*)((char*)a->workspace + L.o_partial);
+    const size_t lds_dec = eval_dec_lds_floats(a->decoder, a->relations, a->embed) * 4;
+    if (const int rc = eval_large_lds(
+            v4 ? (const void*)k_eval_dec<true> : (const void*)k_eval_dec<false>, a))
+        return rc;
+    EvalArgs e = eval_args_of(a, (int)L.chunk, L.enc);
+    e.s = a->neg_samples; e.neg1 = a->neg1; e.neg2 = a->neg2; e.neg_stride = a->neg_stride;
+    float* const terms = e.terms;
     if (a->nrows == 0) {
         hipLaunchKernelGGL(k_eval_acc, dim3(1), dim3(64), 0, st, partial, 0, a->sums_out, 1);
         HIPCHK(hipGetLastError());
@@ -1589,15 +1674,8 @@ extern "C" int rae_eval_cost(const rae_eval_args* a, rae_stream_t stream) {
         const int n = (int)std::min<int64_t>(L.chunk, a->nrows - c0);
         e.row0 = a->row0 + c0;
         e.n = n;
-        e.terms = a->terms_out ? a->terms_out + c0 * 3 : (float*)(ws + L.o_terms);
-        if (bil) {
-            const dim3 ge((unsigned)std::min(ceil_div(n, RAE_EV_NW), 65536));
-            const dim3 gm((unsigned)(eval_nbi(r) * eval_nbj(r)));
-            with_bool(v4, [&](auto V) {
-                hipLaunchKernelGGL(k_eval_enc<RAE_CV(V)>, ge, dim3(RAE_EV_BT), 0, st, e);
-                hipLaunchKernelGGL(k_eval_mt<RAE_CV(V)>, gm, dim3(RAE_EV_MTT), lds_mt, st, e);
-            });
-        }
+        e.terms = a->terms_out ? a->terms_out + c0 * 3 : terms;
+        launch_enc_mt(e, st);
         const dim3 gd((unsigned)ceil_div(n, RAE_EV_TE));
         with_bool(v4, [&](auto V) {
             hipLaunchKernelGGL(k_eval_dec<RAE_CV(V)>, gd, dim3(RAE_EV_BT), lds_dec, st, e);
@@ -1615,41 +1693,46 @@ extern "C" int rae_eval_cost(const rae_eval_args* a, rae_stream_t stream) {
 // ---- argument ranking over all entities -------------------------------------------------------
 namespace {
 struct RankLayout {                          // rae_eval_rank's workspace
-    size_t o_partial, o_terms, o_P, o_v, o_w, o_Q, o_c, o_u, o_skip, o_lse, o_part, total;
+    size_t o_partial, o_lse, o_part, total;
+    EncWs enc;
+    QueryWs q;
 };
 inline size_t rank_part_bytes(int64_t n) {
     return ev_align((size_t)rank_strips(n) * RAE_RK_QCHUNK * sizeof(float2));
 }
-// shapes of rae_rank_queries (host only)
-int rank_shapes(const rae_rank_args* a) {
-    if (!a) return fail(RAE_E_INVALID, "null argument");
-    if (a->embed < 1 || a->embed > 1024) return fail(RAE_E_INVALID, "embed must be in [1, 1024]");
-    if (a->n_entities < 1 || a->n_entities >= (1ll << 31))
-        return fail(RAE_E_INVALID, "n_entities must be in [1, 2^31)");
-    return RAE_OK;
-}
 // shapes of rae_eval_rank and its workspace layout (host only)
 int eval_rank_layout(const rae_eval_args* a, RankLayout& L) {
     if (const int rc = eval_shapes(a, false)) return rc;
-    if (a->n_entities < 1 || a->n_entities >= (1ll << 31))
-        return fail(RAE_E_INVALID, "n_entities must be in [1, 2^31)");
-    const int m = a->relations, r = a->embed;
-    const bool bil = a->decoder != RAE_DEC_SP;
-    const size_t ch = RAE_RK_ROWCHUNK, r4 = (size_t)eval_r4(r);
-    size_t o = 0;
-    L.o_partial = o; o = ev_align(o + (ch / RAE_EV_SUMROWS) * RAE_RK_NSUM * sizeof(double));
-    L.o_terms = o;   o = ev_align(o + ch * 3 * sizeof(float));
-    L.o_P = o;       if (bil) o = ev_align(o + ch * m * sizeof(float));
-    L.o_v = o;       if (bil) o = ev_align(o + (size_t)eval_nbj(r) * ch * r4 * sizeof(float));
-    L.o_w = o;       if (bil) o = ev_align(o + (size_t)eval_nbi(r) * ch * r4 * sizeof(float));
-    L.o_Q = o;       o = ev_align(o + 2 * ch * r4 * sizeof(float));
-    L.o_c = o;       o = ev_align(o + 2 * ch * sizeof(float));
-    L.o_u = o;       o = ev_align(o + 2 * ch * sizeof(float));
-    L.o_skip = o;    o = ev_align(o + 2 * ch * sizeof(int32_t));
+    if (const int rc = entity_count(a->n_entities)) return rc;
+    const size_t ch = RAE_RK_ROWCHUNK;
+    L.o_partial = 0;
+    size_t o = ev_align((ch / RAE_EV_SUMROWS) * RAE_RK_NSUM * sizeof(double));
+    o = lay_queries(a, ch, lay_enc(a, ch, o, L.enc), L.q);
     L.o_lse = o;     o = ev_align(o + 2 * ch * sizeof(float));
     L.o_part = o;    o += rank_part_bytes(a->n_entities);
     L.total = o;
     return RAE_OK;
+}
+// the rank / top-k prelude of one chunk e of RAE_RK_ROWCHUNK rows: its 2 e.n queries built on the
+// stream, and the arguments that rank them (u: where the true entities' scores go, or the
+// workspace's)
+RankArgs rank_queries_of(const EvalArgs& e, const rae_eval_args* a, const QueryWs& L, float* u,
+                         hipStream_t st) {
+    char* ws = (char*)a->workspace;
+    RankBuild b;
+    b.Q = (float*)(ws + L.o_Q);
+    b.c = (float*)(ws + L.o_c);
+    b.u = u ? u : (float*)(ws + L.o_u);
+    b.skip = (int32_t*)(ws + L.o_skip);
+    const dim3 gd((unsigned)ceil_div(e.n, RAE_EV_TE));
+    const size_t lds_dec = eval_dec_lds_floats(e.dec, e.m, e.r) * 4;
+    with_bool((e.m % 4) == 0, [&](auto V) {
+        hipLaunchKernelGGL(k_rank_build<RAE_CV(V)>, gd, dim3(RAE_EV_BT), lds_dec, st, e, b);
+    });
+    RankArgs k;
+    k.Q = b.Q; k.ldq = e.r4; k.add = b.c; k.target = b.u; k.skip = b.skip;
+    k.A = a->A; k.Ab = a->Ab; k.n = a->n_entities; k.r = e.r; k.nq = 2 * e.n;
+    return k;
 }
 // one chunk (k.nq <= RAE_RK_QCHUNK queries) on the stream: zero, scores, the lse's finish
 void rank_launch(RankArgs k, float* lse, hipStream_t st) {
@@ -1675,7 +1758,7 @@ extern "C" int64_t rae_rank_workspace_bytes(const rae_rank_args* q, const rae_ev
     if ((q != nullptr) == (e != nullptr))
         return fail(RAE_E_INVALID, "give exactly one of the two argument structs"), -1;
     if (q) {
-        if (rank_shapes(q)) return -1;
+        if (query_shapes(q->embed, q->n_entities)) return -1;
         return (int64_t)rank_part_bytes(q->n_entities);
     }
     RankLayout L;
@@ -1684,7 +1767,8 @@ extern "C" int64_t rae_rank_workspace_bytes(const rae_rank_args* q, const rae_ev
 }
 
 extern "C" int rae_rank_queries(const rae_rank_args* a, rae_stream_t stream) {
-    if (const int rc = rank_shapes(a)) return rc;
+    if (!a) return fail(RAE_E_INVALID, "null argument");
+    if (const int rc = query_shapes(a->embed, a->n_entities)) return rc;
     if (a->nq < 0) return fail(RAE_E_INVALID, "nq must be >= 0");
     if (a->ldq < a->embed) return fail(RAE_E_INVALID, "ldq is smaller than embed");
     if (a->ldq % 4) return fail(RAE_E_INVALID, "ldq must be a multiple of 4");
@@ -1696,10 +1780,9 @@ extern "C" int rae_rank_queries(const rae_rank_args* a, rae_stream_t stream) {
     if ((a->embed % 4) == 0 && ((uintptr_t)a->A & 15))
         return fail(RAE_E_INVALID, "A must be 16-byte aligned");
     if (!a->greater || !a->equal) return fail(RAE_E_INVALID, "greater / equal is NULL");
-    if (!a->workspace) return fail(RAE_E_INVALID, "workspace is NULL");
-    if ((uintptr_t)a->workspace & 255) return fail(RAE_E_INVALID, "workspace must be 256-byte aligned");
-    if (a->workspace_bytes < (int64_t)rank_part_bytes(a->n_entities))
-        return fail(RAE_E_INVALID, "workspace_bytes is smaller than rae_rank_workspace_bytes()");
+    if (const int rc = check_workspace(a->workspace, a->workspace_bytes,
+                                       rank_part_bytes(a->n_entities), "rae_rank_workspace_bytes"))
+        return rc;
     hipStream_t st = (hipStream_t)stream;
     for (int64_t c0 = 0; c0 < a->nq; c0 += RAE_RK_QCHUNK) {
         RankArgs k;
@@ -1721,53 +1804,21 @@ extern "C" int rae_eval_rank(const rae_eval_args* a, const rae_rank_out* out, ra
     RankLayout L;
     if (const int rc = eval_rank_layout(a, L)) return rc;
     if (!out) return fail(RAE_E_INVALID, "out is NULL");
-    if (a->nrows < 0) return fail(RAE_E_INVALID, "nrows must be >= 0");
-    if (a->row0 < 0 || a->row0 + a->nrows >= (1ll << 31))
-        return fail(RAE_E_INVALID, "row0 / nrows out of range");
-    const int m = a->relations, r = a->embed;
-    const bool bil = a->decoder != RAE_DEC_SP, v4 = (m % 4) == 0;
-    if (!a->W) return fail(RAE_E_INVALID, "W is NULL");
-    if (!a->Wb) return fail(RAE_E_INVALID, "Wb is NULL");
-    if (!a->A) return fail(RAE_E_INVALID, "A is NULL");
-    if (!a->Ab) return fail(RAE_E_INVALID, "Ab is NULL");
-    if (a->decoder != RAE_DEC_RESCAL && (!a->C1 || !a->C2))
-        return fail(RAE_E_INVALID, "C1 / C2 is NULL");
-    if (bil && !a->R3) return fail(RAE_E_INVALID, "R3 is NULL");
-    if (!a->indptr || !a->indices) return fail(RAE_E_INVALID, "indptr / indices is NULL");
-    if (!a->args1 || !a->args2) return fail(RAE_E_INVALID, "args1 / args2 is NULL");
+    if (const int rc = check_rows(a)) return rc;
+    if (const int rc = check_model(a)) return rc;
     if (a->nrows > 0 && (!out->greater || !out->equal))
         return fail(RAE_E_INVALID, "greater / equal is NULL");
-    if (!a->workspace) return fail(RAE_E_INVALID, "workspace is NULL");
-    if ((uintptr_t)a->workspace & 255) return fail(RAE_E_INVALID, "workspace must be 256-byte aligned");
-    if (a->workspace_bytes < (int64_t)L.total)
-        return fail(RAE_E_INVALID, "workspace_bytes is smaller than rae_rank_workspace_bytes()");
-    if (v4 && (((uintptr_t)a->W | (uintptr_t)a->Wb | (uintptr_t)a->C1 | (uintptr_t)a->C2 |
-                (uintptr_t)a->R3) & 15))
-        return fail(RAE_E_INVALID, "W / Wb / C1 / C2 / R3 must be 16-byte aligned");
-    if ((r % 4) == 0 && ((uintptr_t)a->A & 15))
-        return fail(RAE_E_INVALID, "A must be 16-byte aligned");
+    if (const int rc = check_workspace(a->workspace, a->workspace_bytes, L.total,
+                                       "rae_rank_workspace_bytes"))
+        return rc;
+    if (const int rc = check_align(a)) return rc;
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)a->workspace;
     double* partial = (double*)(ws + L.o_partial);
-    const size_t lds_dec = eval_dec_lds_floats(a->decoder, m, r) * 4;
-    const size_t lds_mt = eval_mt_lds_bytes(m);
-    if (lds_dec > 48 * 1024) {
-        HIPCHK(hipFuncSetAttribute(v4 ? (const void*)k_rank_build<true> : (const void*)k_rank_build<false>,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_dec));
-    }
-    if (bil && lds_mt > 48 * 1024) {
-        HIPCHK(hipFuncSetAttribute(v4 ? (const void*)k_eval_mt<true> : (const void*)k_eval_mt<false>,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_mt));
-    }
-    EvalArgs e;
-    e.dec = a->decoder; e.m = m; e.r = r; e.s = 0; e.alpha = a->alpha;
-    e.W = a->W; e.Wb = a->Wb; e.A = a->A; e.Ab = a->Ab; e.C1 = a->C1; e.C2 = a->C2; e.R3 = a->R3;
-    e.indptr = a->indptr; e.indices = a->indices; e.values = a->values;
-    e.args1 = a->args1; e.args2 = a->args2; e.neg1 = nullptr; e.neg2 = nullptr;
-    e.neg_stride = 0;
-    e.cap = RAE_RK_ROWCHUNK; e.r4 = eval_r4(r);
-    e.terms = (float*)(ws + L.o_terms);
-    e.P = (float*)(ws + L.o_P); e.vpart = (float*)(ws + L.o_v); e.wpart = (float*)(ws + L.o_w);
+    if (const int rc = eval_large_lds((a->relations % 4) == 0 ? (const void*)k_rank_build<true>
+                                                               : (const void*)k_rank_build<false>, a))
+        return rc;
+    EvalArgs e = eval_args_of(a, RAE_RK_ROWCHUNK, L.enc);
     const bool want_lse = out->lse || out->summary;
     RankHits hk;
     for (int j = 0; j < 4; ++j) hk.k[j] = out->hits_k[j];
@@ -1783,26 +1834,8 @@ extern "C" int rae_eval_rank(const rae_eval_args* a, const rae_rank_out* out, ra
         const int n = (int)std::min<int64_t>(RAE_RK_ROWCHUNK, a->nrows - c0);
         e.row0 = a->row0 + c0;
         e.n = n;
-        if (bil) {
-            const dim3 ge((unsigned)std::min(ceil_div(n, RAE_EV_NW), 65536));
-            const dim3 gm((unsigned)(eval_nbi(r) * eval_nbj(r)));
-            with_bool(v4, [&](auto V) {
-                hipLaunchKernelGGL(k_eval_enc<RAE_CV(V)>, ge, dim3(RAE_EV_BT), 0, st, e);
-                hipLaunchKernelGGL(k_eval_mt<RAE_CV(V)>, gm, dim3(RAE_EV_MTT), lds_mt, st, e);
-            });
-        }
-        RankBuild b;
-        b.Q = (float*)(ws + L.o_Q);
-        b.c = (float*)(ws + L.o_c);
-        b.u = out->target ? out->target + 2 * c0 : (float*)(ws + L.o_u);
-        b.skip = (int32_t*)(ws + L.o_skip);
-        const dim3 gd((unsigned)ceil_div(n, RAE_EV_TE));
-        with_bool(v4, [&](auto V) {
-            hipLaunchKernelGGL(k_rank_build<RAE_CV(V)>, gd, dim3(RAE_EV_BT), lds_dec, st, e, b);
-        });
-        RankArgs k;
-        k.Q = b.Q; k.ldq = e.r4; k.add = b.c; k.target = b.u; k.skip = b.skip;
-        k.A = a->A; k.Ab = a->Ab; k.n = a->n_entities; k.r = r; k.nq = 2 * n;
+        launch_enc_mt(e, st);
+        RankArgs k = rank_queries_of(e, a, L.q, out->target ? out->target + 2 * c0 : nullptr, st);
         k.greater = out->greater + 2 * c0; k.equal = out->equal + 2 * c0;
         k.part = (float2*)(ws + L.o_part);
         float* lse = !want_lse ? nullptr : (out->lse ? out->lse + 2 * c0 : (float*)(ws + L.o_lse));
@@ -1811,7 +1844,7 @@ extern "C" int rae_eval_rank(const rae_eval_args* a, const rae_rank_out* out, ra
             const int nblk = ceil_div(n, RAE_EV_SUMROWS);
             hipLaunchKernelGGL(k_rank_blocksum, dim3((unsigned)nblk), dim3(RAE_EV_BT), 0, st,
                                (const int32_t*)k.greater, (const int32_t*)k.equal,
-                               (const float*)b.u, (const float*)lse, n, hk, partial);
+                               (const float*)k.target, (const float*)lse, n, hk, partial);
             hipLaunchKernelGGL(k_rank_acc, dim3(1), dim3(64), 0, st, (const double*)partial, nblk,
                                out->summary, c0 == 0 ? 1 : 0);
         }
@@ -1823,7 +1856,9 @@ extern "C" int rae_eval_rank(const rae_eval_args* a, const rae_rank_out* out, ra
 // ---- top-k entity retrieval ---------------------------------------------------------------------
 namespace {
 struct TopkLayout {                          // rae_eval_topk's workspace
-    size_t o_terms, o_P, o_v, o_w, o_Q, o_c, o_u, o_skip, o_keys, total;
+    size_t o_keys, total;
+    EncWs enc;
+    QueryWs q;
 };
 // the strips' kept lists of one round of RAE_ETK_QCHUNK queries
 inline size_t topk_keys_bytes(int64_t n, int top) {
@@ -1833,34 +1868,14 @@ int topk_top(int32_t top) {
     if (top < 1 || top > RAE_ETK_MAXTOP) return fail(RAE_E_INVALID, "top must be in [1, 32]");
     return RAE_OK;
 }
-// shapes of rae_topk_queries (host only)
-int topk_shapes(const rae_topk_args* a) {
-    if (!a) return fail(RAE_E_INVALID, "null argument");
-    if (a->embed < 1 || a->embed > 1024) return fail(RAE_E_INVALID, "embed must be in [1, 1024]");
-    if (a->n_entities < 1 || a->n_entities >= (1ll << 31))
-        return fail(RAE_E_INVALID, "n_entities must be in [1, 2^31)");
-    return RAE_OK;
-}
 // shapes of rae_eval_topk and its workspace layout (host only)
 int eval_topk_layout(const rae_eval_args* a, int32_t top, TopkLayout& L) {
     if (const int rc = eval_shapes(a, false)) return rc;
-    if (a->n_entities < 1 || a->n_entities >= (1ll << 31))
-        return fail(RAE_E_INVALID, "n_entities must be in [1, 2^31)");
+    if (const int rc = entity_count(a->n_entities)) return rc;
     if (const int rc = topk_top(top)) return rc;
-    const int m = a->relations, r = a->embed;
-    const bool bil = a->decoder != RAE_DEC_SP;
-    const size_t ch = RAE_RK_ROWCHUNK, r4 = (size_t)eval_r4(r);
-    size_t o = 0;
-    L.o_terms = o;   o = ev_align(o + ch * 3 * sizeof(float));
-    L.o_P = o;       if (bil) o = ev_align(o + ch * m * sizeof(float));
-    L.o_v = o;       if (bil) o = ev_align(o + (size_t)eval_nbj(r) * ch * r4 * sizeof(float));
-    L.o_w = o;       if (bil) o = ev_align(o + (size_t)eval_nbi(r) * ch * r4 * sizeof(float));
-    L.o_Q = o;       o = ev_align(o + 2 * ch * r4 * sizeof(float));
-    L.o_c = o;       o = ev_align(o + 2 * ch * sizeof(float));
-    L.o_u = o;       o = ev_align(o + 2 * ch * sizeof(float));
-    L.o_skip = o;    o = ev_align(o + 2 * ch * sizeof(int32_t));
-    L.o_keys = o;    o += topk_keys_bytes(a->n_entities, top);
-    L.total = o;
+    const size_t ch = RAE_RK_ROWCHUNK;
+    L.o_keys = lay_queries(a, ch, lay_enc(a, ch, 0, L.enc), L.q);
+    L.total = L.o_keys + topk_keys_bytes(a->n_entities, top);
     return RAE_OK;
 }
 // k.nq queries on the stream in rounds of RAE_ETK_QCHUNK: selection per strip, then the merge
@@ -1900,7 +1915,7 @@ extern "C" int64_t rae_topk_workspace_bytes(const rae_topk_args* q, const rae_ev
     if ((q != nullptr) == (e != nullptr))
         return fail(RAE_E_INVALID, "give exactly one of the two argument structs"), -1;
     if (q) {
-        if (topk_shapes(q) || topk_top(top)) return -1;
+        if (query_shapes(q->embed, q->n_entities) || topk_top(top)) return -1;
         return (int64_t)topk_keys_bytes(q->n_entities, top);
     }
     TopkLayout L;
@@ -1909,7 +1924,8 @@ extern "C" int64_t rae_topk_workspace_bytes(const rae_topk_args* q, const rae_ev
 }
 
 extern "C" int rae_topk_queries(const rae_topk_args* a, rae_stream_t stream) {
-    if (const int rc = topk_shapes(a)) return rc;
+    if (!a) return fail(RAE_E_INVALID, "null argument");
+    if (const int rc = query_shapes(a->embed, a->n_entities)) return rc;
     if (const int rc = topk_top(a->top)) return rc;
     if (a->nq < 0) return fail(RAE_E_INVALID, "nq must be >= 0");
     if (a->ldq < a->embed) return fail(RAE_E_INVALID, "ldq is smaller than embed");
@@ -1921,10 +1937,10 @@ extern "C" int rae_topk_queries(const rae_topk_args* a, rae_stream_t stream) {
     if ((a->embed % 4) == 0 && ((uintptr_t)a->A & 15))
         return fail(RAE_E_INVALID, "A must be 16-byte aligned");
     if (!a->ents_out) return fail(RAE_E_INVALID, "ents_out is NULL");
-    if (!a->workspace) return fail(RAE_E_INVALID, "workspace is NULL");
-    if ((uintptr_t)a->workspace & 255) return fail(RAE_E_INVALID, "workspace must be 256-byte aligned");
-    if (a->workspace_bytes < (int64_t)topk_keys_bytes(a->n_entities, a->top))
-        return fail(RAE_E_INVALID, "workspace_bytes is smaller than rae_topk_workspace_bytes()");
+    if (const int rc = check_workspace(a->workspace, a->workspace_bytes,
+                                       topk_keys_bytes(a->n_entities, a->top),
+                                       "rae_topk_workspace_bytes"))
+        return rc;
     RankArgs k;
     k.Q = a->Q; k.ldq = a->ldq; k.add = a->add; k.skip = a->skip;
     k.A = a->A; k.Ab = a->Ab; k.n = a->n_entities; k.r = a->embed; k.nq = 0;
@@ -1936,77 +1952,29 @@ extern "C" int rae_eval_topk(const rae_eval_args* a, const rae_topk_out* out, ra
     if (!out) return fail(RAE_E_INVALID, "out is NULL");
     TopkLayout L;
     if (const int rc = eval_topk_layout(a, out->top, L)) return rc;
-    if (a->nrows < 0) return fail(RAE_E_INVALID, "nrows must be >= 0");
-    if (a->row0 < 0 || a->row0 + a->nrows >= (1ll << 31))
-        return fail(RAE_E_INVALID, "row0 / nrows out of range");
-    const int m = a->relations, r = a->embed, top = out->top;
-    const bool bil = a->decoder != RAE_DEC_SP, v4 = (m % 4) == 0;
-    if (!a->W) return fail(RAE_E_INVALID, "W is NULL");
-    if (!a->Wb) return fail(RAE_E_INVALID, "Wb is NULL");
-    if (!a->A) return fail(RAE_E_INVALID, "A is NULL");
-    if (!a->Ab) return fail(RAE_E_INVALID, "Ab is NULL");
-    if (a->decoder != RAE_DEC_RESCAL && (!a->C1 || !a->C2))
-        return fail(RAE_E_INVALID, "C1 / C2 is NULL");
-    if (bil && !a->R3) return fail(RAE_E_INVALID, "R3 is NULL");
-    if (!a->indptr || !a->indices) return fail(RAE_E_INVALID, "indptr / indices is NULL");
-    if (!a->args1 || !a->args2) return fail(RAE_E_INVALID, "args1 / args2 is NULL");
+    if (const int rc = check_rows(a)) return rc;
+    if (const int rc = check_model(a)) return rc;
     if (a->nrows > 0 && !out->ents) return fail(RAE_E_INVALID, "ents is NULL");
-    if (!a->workspace) return fail(RAE_E_INVALID, "workspace is NULL");
-    if ((uintptr_t)a->workspace & 255) return fail(RAE_E_INVALID, "workspace must be 256-byte aligned");
-    if (a->workspace_bytes < (int64_t)L.total)
-        return fail(RAE_E_INVALID, "workspace_bytes is smaller than rae_topk_workspace_bytes()");
-    if (v4 && (((uintptr_t)a->W | (uintptr_t)a->Wb | (uintptr_t)a->C1 | (uintptr_t)a->C2 |
-                (uintptr_t)a->R3) & 15))
-        return fail(RAE_E_INVALID, "W / Wb / C1 / C2 / R3 must be 16-byte aligned");
-    if ((r % 4) == 0 && ((uintptr_t)a->A & 15))
-        return fail(RAE_E_INVALID, "A must be 16-byte aligned");
+    if (const int rc = check_workspace(a->workspace, a->workspace_bytes, L.total,
+                                       "rae_topk_workspace_bytes"))
+        return rc;
+    if (const int rc = check_align(a)) return rc;
     if (a->nrows == 0) return RAE_OK;         // nothing is written
     hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)a->workspace;
-    const size_t lds_dec = eval_dec_lds_floats(a->decoder, m, r) * 4;
-    const size_t lds_mt = eval_mt_lds_bytes(m);
-    if (lds_dec > 48 * 1024) {
-        HIPCHK(hipFuncSetAttribute(v4 ? (const void*)k_rank_build<true> : (const void*)k_rank_build<false>,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_dec));
-    }
-    if (bil && lds_mt > 48 * 1024) {
-        HIPCHK(hipFuncSetAttribute(v4 ? (const void*)k_eval_mt<true> : (const void*)k_eval_mt<false>,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_mt));
-    }
-    EvalArgs e;
-    e.dec = a->decoder; e.m = m; e.r = r; e.s = 0; e.alpha = a->alpha;
-    e.W = a->W; e.Wb = a->Wb; e.A = a->A; e.Ab = a->Ab; e.C1 = a->C1; e.C2 = a->C2; e.R3 = a->R3;
-    e.indptr = a->indptr; e.indices = a->indices; e.values = a->values;
-    e.args1 = a->args1; e.args2 = a->args2; e.neg1 = nullptr; e.neg2 = nullptr;
-    e.neg_stride = 0;
-    e.cap = RAE_RK_ROWCHUNK; e.r4 = eval_r4(r);
-    e.terms = (float*)(ws + L.o_terms);  // the encoder's entropy term lands here, unread
-    e.P = (float*)(ws + L.o_P); e.vpart = (float*)(ws + L.o_v); e.wpart = (float*)(ws + L.o_w);
+    const int top = out->top;
+    if (const int rc = eval_large_lds((a->relations % 4) == 0 ? (const void*)k_rank_build<true>
+                                                               : (const void*)k_rank_build<false>, a))
+        return rc;
+    EvalArgs e = eval_args_of(a, RAE_RK_ROWCHUNK, L.enc);   // the entropy term lands in terms, unread
     for (int64_t c0 = 0; c0 < a->nrows; c0 += RAE_RK_ROWCHUNK) {
         const int n = (int)std::min<int64_t>(RAE_RK_ROWCHUNK, a->nrows - c0);
         e.row0 = a->row0 + c0;
         e.n = n;
-        if (bil) {
-            const dim3 ge((unsigned)std::min(ceil_div(n, RAE_EV_NW), 65536));
-            const dim3 gm((unsigned)(eval_nbi(r) * eval_nbj(r)));
-            with_bool(v4, [&](auto V) {
-                hipLaunchKernelGGL(k_eval_enc<RAE_CV(V)>, ge, dim3(RAE_EV_BT), 0, st, e);
-                hipLaunchKernelGGL(k_eval_mt<RAE_CV(V)>, gm, dim3(RAE_EV_MTT), lds_mt, st, e);
-            });
-        }
-        RankBuild b;
-        b.Q = (float*)(ws + L.o_Q);
-        b.c = (float*)(ws + L.o_c);
-        b.u = (float*)(ws + L.o_u);
-        b.skip = (int32_t*)(ws + L.o_skip);
-        const dim3 gd((unsigned)ceil_div(n, RAE_EV_TE));
-        with_bool(v4, [&](auto V) {
-            hipLaunchKernelGGL(k_rank_build<RAE_CV(V)>, gd, dim3(RAE_EV_BT), lds_dec, st, e, b);
-        });
-        RankArgs k;
-        k.Q = b.Q; k.ldq = e.r4; k.add = b.c; k.skip = out->skip_true ? b.skip : nullptr;
-        k.A = a->A; k.Ab = a->Ab; k.n = a->n_entities; k.r = r; k.nq = 0;
-        if (const int rc = topk_launch(k, 2 * (int64_t)n, top, (rae_key64*)(ws + L.o_keys),
+        launch_enc_mt(e, st);
+        RankArgs k = rank_queries_of(e, a, L.q, nullptr, st);
+        if (!out->skip_true) k.skip = nullptr;
+        if (const int rc = topk_launch(k, 2 * (int64_t)n, top,
+                                       (rae_key64*)((char*)a->workspace + L.o_keys),
                                        out->ents + 2 * c0 * top,
                                        out->scores ? out->scores + 2 * c0 * top : nullptr, st))
             return rc;
@@ -2017,22 +1985,9 @@ extern "C" int rae_eval_topk(const rae_eval_args* a, const rae_topk_out* out, ra
 // ---- relation scores from the decoder -----------------------------------------------------------
 namespace {
 struct RelLayout { size_t o_psi, o_lsm, total; };
-// the shapes of the relation-score kernel (host only): rae_eval_cost's limits
-int rel_shapes(int dec, int m, int r, int64_t n_entities) {
-    if (dec < 0 || dec > 2) return fail(RAE_E_INVALID, "decoder must be 0..2");
-    if (m < 1 || m > 512) return fail(RAE_E_INVALID, "relations must be in [1, 512]");
-    if ((m % 4) != 0 && m > 128)
-        return fail(RAE_E_INVALID, "relations must be a multiple of 4 above 128");
-    if (r < 1 || r > 1024) return fail(RAE_E_INVALID, "embed must be in [1, 1024]");
-    if (dec != RAE_DEC_SP && m > 320)
-        return fail(RAE_E_INVALID, "relations must be <= 320 for the bilinear decoders");
-    if (n_entities < 1 || n_entities >= (1ll << 31))
-        return fail(RAE_E_INVALID, "n_entities must be in [1, 2^31)");
-    return RAE_OK;
-}
 int eval_rel_layout(const rae_eval_args* a, RelLayout& L) {
     if (const int rc = eval_shapes(a, false)) return rc;
-    if (const int rc = rel_shapes(a->decoder, a->relations, a->embed, a->n_entities)) return rc;
+    if (const int rc = entity_count(a->n_entities)) return rc;
     const size_t per = ev_align((size_t)RAE_RS_ROUND * a->relations * sizeof(float));
     L.o_psi = 0; L.o_lsm = per; L.total = 2 * per;
     return RAE_OK;
@@ -2121,30 +2076,14 @@ extern "C" int rae_eval_relations(const rae_eval_args* a, const rae_rel_out* out
     if (!out) return fail(RAE_E_INVALID, "out is NULL");
     if (!out->psi && !out->joint && !out->labels_dec && !out->labels_joint)
         return fail(RAE_E_INVALID, "all four outputs are NULL");
-    if (a->nrows < 0) return fail(RAE_E_INVALID, "nrows must be >= 0");
-    if (a->row0 < 0 || a->row0 + a->nrows >= (1ll << 31))
-        return fail(RAE_E_INVALID, "row0 / nrows out of range");
-    const int m = a->relations, r = a->embed;
-    const bool bil = a->decoder != RAE_DEC_SP, v4 = (m % 4) == 0;
-    if (!a->W) return fail(RAE_E_INVALID, "W is NULL");
-    if (!a->Wb) return fail(RAE_E_INVALID, "Wb is NULL");
-    if (!a->A) return fail(RAE_E_INVALID, "A is NULL");
-    if (!a->Ab) return fail(RAE_E_INVALID, "Ab is NULL");
-    if (a->decoder != RAE_DEC_RESCAL && (!a->C1 || !a->C2))
-        return fail(RAE_E_INVALID, "C1 / C2 is NULL");
-    if (bil && !a->R3) return fail(RAE_E_INVALID, "R3 is NULL");
-    if (!a->indptr || !a->indices) return fail(RAE_E_INVALID, "indptr / indices is NULL");
-    if (!a->args1 || !a->args2) return fail(RAE_E_INVALID, "args1 / args2 is NULL");
-    if (!a->workspace) return fail(RAE_E_INVALID, "workspace is NULL");
-    if ((uintptr_t)a->workspace & 255) return fail(RAE_E_INVALID, "workspace must be 256-byte aligned");
-    if (a->workspace_bytes < (int64_t)L.total)
-        return fail(RAE_E_INVALID, "workspace_bytes is smaller than rae_relscore_workspace_bytes()");
-    if (v4 && (((uintptr_t)a->W | (uintptr_t)a->Wb | (uintptr_t)a->C1 | (uintptr_t)a->C2 |
-                (uintptr_t)a->R3) & 15))
-        return fail(RAE_E_INVALID, "W / Wb / C1 / C2 / R3 must be 16-byte aligned");
-    if ((r % 4) == 0 && ((uintptr_t)a->A & 15))
-        return fail(RAE_E_INVALID, "A must be 16-byte aligned");
+    if (const int rc = check_rows(a)) return rc;
+    if (const int rc = check_model(a)) return rc;
+    if (const int rc = check_workspace(a->workspace, a->workspace_bytes, L.total,
+                                       "rae_relscore_workspace_bytes"))
+        return rc;
+    if (const int rc = check_align(a)) return rc;
     if (a->nrows == 0) return RAE_OK;         // nothing is read or written
+    const int m = a->relations, r = a->embed;
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)a->workspace;
     const bool want_joint = out->joint || out->labels_joint;

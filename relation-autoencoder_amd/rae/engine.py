@@ -911,37 +911,55 @@ class TrainEngine:
         ent = -2.0 * sh_ / D if nrows else 0.0
         return EvalResult(rec + ent, rec, ent, out, (sp_, sh_, sn_))
 
+    def _eval_args(self, split: DeviceSplit | None, row0: int = 0, nrows: int = 0,
+                   shift: int = 0):
+        """rae_eval_args of the plan-free evaluation entries: the engine's shapes and parameters,
+        and rows [row0, row0+nrows) of `split` viewed from row `shift` on (None: no rows).
+        Negatives, outputs and the workspace are the caller's to add."""
+        named = self._named
+        R3 = named.get("R", named.get("C"))
+        a = _lib.RaeEvalArgs()
+        a.decoder = self.cfg.decoder
+        a.relations, a.embed = self.m, self.r
+        a.n_entities = self.cfg.n_entities
+        a.alpha = self.cfg.alpha
+        p = _lib.ptr
+        a.W, a.Wb, a.A, a.Ab = p(named["W"]), p(named["Wb"]), p(named["A"]), p(named["Ab"])
+        a.C1, a.C2, a.R3 = p(named.get("C1")), p(named.get("C2")), p(R3)
+        if split is not None:
+            a.indptr = split.indptr.data_ptr() + 4 * shift
+            a.indices, a.values = p(split.indices), p(split.values)
+            a.args1 = split.args1.data_ptr() + 4 * shift
+            a.args2 = split.args2.data_ptr() + 4 * shift
+        a.row0, a.nrows = int(row0), int(nrows)
+        return a
+
+    def _workspace(self, a, attr: str, what: str, size):
+        """Point a's workspace at the device buffer self.<attr>, allocated once per engine with
+        the bytes the sizing call size() asks for (`what` names it in the error)."""
+        if getattr(self, attr, None) is None:
+            need = int(size())
+            if need < 0:
+                _lib.check(-1, what)
+            setattr(self, attr, torch.empty(max(need, 256), dtype=torch.uint8, device=self.device))
+        ws = getattr(self, attr)
+        a.workspace, a.workspace_bytes = _lib.ptr(ws), int(ws.numel())
+
     def queue_evaluate(self, split: DeviceSplit, row0: int, nrows: int, n1, n2, out=None,
                        shift: int = 0):
         """Queue rae_eval_cost on the current stream (no host synchronisation): rows
         [row0, row0+nrows) of `split` viewed from row `shift` on, negatives n1 / n2 (device int32,
         (s, stride)), terms into `out` ((nrows, 3) fp32 or None), the sums into self._eval_sums.
         evaluate() is this plus the read-back; tools/eval_bench.py times it alone."""
-        named = self._named
-        R3 = named.get("R", named.get("C"))
-        a = _lib.RaeEvalArgs()
-        a.decoder = self.cfg.decoder
-        a.relations, a.embed, a.neg_samples = self.m, self.r, self.s
-        a.n_entities = self.cfg.n_entities
-        a.alpha = self.cfg.alpha
-        p = _lib.ptr
-        a.W, a.Wb, a.A, a.Ab = p(named["W"]), p(named["Wb"]), p(named["A"]), p(named["Ab"])
-        a.C1, a.C2, a.R3 = p(named.get("C1")), p(named.get("C2")), p(R3)
-        a.indptr = split.indptr.data_ptr() + 4 * shift
-        a.indices, a.values = p(split.indices), p(split.values)
-        a.args1 = split.args1.data_ptr() + 4 * shift
-        a.args2 = split.args2.data_ptr() + 4 * shift
-        a.neg1, a.neg2, a.neg_stride = p(n1), p(n2), int(n1.shape[1])
-        a.row0, a.nrows = int(row0), int(nrows)
-        if getattr(self, "_eval_ws", None) is None:      # once per engine
-            need = int(self.lib.rae_eval_workspace_bytes(C.byref(a)))
-            if need < 0:
-                _lib.check(-1, "rae_eval_workspace_bytes")
-            self._eval_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+        a = self._eval_args(split, row0, nrows, shift)
+        a.neg_samples = self.s
+        a.neg1, a.neg2, a.neg_stride = _lib.ptr(n1), _lib.ptr(n2), int(n1.shape[1])
+        self._workspace(a, "_eval_ws", "rae_eval_workspace_bytes",
+                        lambda: self.lib.rae_eval_workspace_bytes(C.byref(a)))
+        if getattr(self, "_eval_sums", None) is None:    # once per engine
             self._eval_sums = torch.zeros(3, dtype=torch.float64, device=self.device)
-        a.terms_out = p(out)
-        a.sums_out = p(self._eval_sums)
-        a.workspace, a.workspace_bytes = p(self._eval_ws), int(self._eval_ws.numel())
+        a.terms_out = _lib.ptr(out)
+        a.sums_out = _lib.ptr(self._eval_sums)
         _lib.check(self.lib.rae_eval_cost(C.byref(a), self._stream()), "rae_eval_cost")
 
     # ------------------------------------------------------------------ argument ranking
@@ -984,31 +1002,17 @@ class TrainEngine:
         target, lse), (nrows, 2) each (allocated here unless given; target / lse only with
         per_query).  Returns `out`.  rank() is this plus the read-back;
         tools/rank_eval_bench.py times it alone."""
-        named = self._named
-        R3 = named.get("R", named.get("C"))
-        a = _lib.RaeEvalArgs()
-        a.decoder = self.cfg.decoder
-        a.relations, a.embed = self.m, self.r
-        a.n_entities = self.cfg.n_entities
-        a.alpha = self.cfg.alpha
+        a = self._eval_args(split, row0, nrows)
         p = _lib.ptr
-        a.W, a.Wb, a.A, a.Ab = p(named["W"]), p(named["Wb"]), p(named["A"]), p(named["Ab"])
-        a.C1, a.C2, a.R3 = p(named.get("C1")), p(named.get("C2")), p(R3)
-        a.indptr, a.indices, a.values = p(split.indptr), p(split.indices), p(split.values)
-        a.args1, a.args2 = p(split.args1), p(split.args2)
-        a.row0, a.nrows = int(row0), int(nrows)
-        if getattr(self, "_rank_ws", None) is None:      # once per engine
-            need = int(self.lib.rae_rank_workspace_bytes(None, C.byref(a)))
-            if need < 0:
-                _lib.check(-1, "rae_rank_workspace_bytes")
-            self._rank_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+        self._workspace(a, "_rank_ws", "rae_rank_workspace_bytes",
+                        lambda: self.lib.rae_rank_workspace_bytes(None, C.byref(a)))
+        if getattr(self, "_rank_summary", None) is None:  # once per engine
             self._rank_summary = torch.zeros(16, dtype=torch.float64, device=self.device)
         if out is None:
             mk = lambda dt: torch.empty((nrows, 2), dtype=dt, device=self.device)
             out = (mk(torch.int32), mk(torch.int32),
                    mk(torch.float32) if per_query else None,
                    mk(torch.float32) if per_query else None)
-        a.workspace, a.workspace_bytes = p(self._rank_ws), int(self._rank_ws.numel())
         o = _lib.RaeRankOut()
         o.greater, o.equal, o.target, o.lse = p(out[0]), p(out[1]), p(out[2]), p(out[3])
         o.summary = p(self._rank_summary)
@@ -1021,29 +1025,15 @@ class TrainEngine:
     def _topk_args(self, split: DeviceSplit | None, row0: int = 0, nrows: int = 0):
         """rae_eval_args of rae_eval_topk (the fields rae_eval_rank reads) with the engine's
         top-k workspace, allocated once per engine for top = 32."""
-        named = self._named
-        R3 = named.get("R", named.get("C"))
-        a = _lib.RaeEvalArgs()
-        a.decoder = self.cfg.decoder
-        a.relations, a.embed = self.m, self.r
-        a.n_entities = self.cfg.n_entities
-        a.alpha = self.cfg.alpha
-        p = _lib.ptr
-        a.W, a.Wb, a.A, a.Ab = p(named["W"]), p(named["Wb"]), p(named["A"]), p(named["Ab"])
-        a.C1, a.C2, a.R3 = p(named.get("C1")), p(named.get("C2")), p(R3)
-        if split is not None:
-            a.indptr, a.indices, a.values = p(split.indptr), p(split.indices), p(split.values)
-            a.args1, a.args2 = p(split.args1), p(split.args2)
-        a.row0, a.nrows = int(row0), int(nrows)
-        if getattr(self, "_topk_ws", None) is None:      # once per engine, for both entries
+        a = self._eval_args(split, row0, nrows)
+
+        def need():                                      # for both entries
             q = _lib.RaeTopkArgs()
             q.n_entities, q.embed = self.cfg.n_entities, self.r
-            need = max(int(self.lib.rae_topk_workspace_bytes(None, C.byref(a), _lib.RAE_ETK_MAXTOP)),
-                       int(self.lib.rae_topk_workspace_bytes(C.byref(q), None, _lib.RAE_ETK_MAXTOP)))
-            if need < 0:
-                _lib.check(-1, "rae_topk_workspace_bytes")
-            self._topk_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
-        a.workspace, a.workspace_bytes = p(self._topk_ws), int(self._topk_ws.numel())
+            size = self.lib.rae_topk_workspace_bytes
+            return max(int(size(None, C.byref(a), _lib.RAE_ETK_MAXTOP)),
+                       int(size(C.byref(q), None, _lib.RAE_ETK_MAXTOP)))
+        self._workspace(a, "_topk_ws", "rae_topk_workspace_bytes", need)
         return a
 
     @staticmethod
@@ -1133,25 +1123,9 @@ class TrainEngine:
 
     def _rel_eval_args(self, split: DeviceSplit, row0: int, nrows: int):
         """rae_eval_args of rae_eval_relations with the engine's workspace (once per engine)."""
-        named = self._named
-        R3 = named.get("R", named.get("C"))
-        a = _lib.RaeEvalArgs()
-        a.decoder = self.cfg.decoder
-        a.relations, a.embed = self.m, self.r
-        a.n_entities = self.cfg.n_entities
-        a.alpha = self.cfg.alpha
-        p = _lib.ptr
-        a.W, a.Wb, a.A, a.Ab = p(named["W"]), p(named["Wb"]), p(named["A"]), p(named["Ab"])
-        a.C1, a.C2, a.R3 = p(named.get("C1")), p(named.get("C2")), p(R3)
-        a.indptr, a.indices, a.values = p(split.indptr), p(split.indices), p(split.values)
-        a.args1, a.args2 = p(split.args1), p(split.args2)
-        a.row0, a.nrows = int(row0), int(nrows)
-        if getattr(self, "_rel_ws", None) is None:
-            need = int(self.lib.rae_relscore_workspace_bytes(None, C.byref(a)))
-            if need < 0:
-                _lib.check(-1, "rae_relscore_workspace_bytes")
-            self._rel_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
-        a.workspace, a.workspace_bytes = p(self._rel_ws), int(self._rel_ws.numel())
+        a = self._eval_args(split, row0, nrows)
+        self._workspace(a, "_rel_ws", "rae_relscore_workspace_bytes",
+                        lambda: self.lib.rae_relscore_workspace_bytes(None, C.byref(a)))
         return a
 
     def relation_scores(self, e1, e2):
