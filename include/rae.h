@@ -182,7 +182,10 @@ int rae_version(void);
  * the Python binding refuses a library whose id differs from the sources beside it       */
 const char* rae_build_id(void);
 
-/* floats per example record and per global batch in the exchange buffer */
+/* floats per example record and per global batch in the exchange buffer.  A plan needs
+ * rae_exchange_floats() < 2^30 (4 GiB; rae_plan_create returns RAE_E_INVALID otherwise): the
+ * update reads a record through a buffer resource at a 32-bit byte offset from the buffer's
+ * base, so records at or beyond 2^30 floats cannot be addressed.                          */
 int64_t rae_exchange_record_floats(const rae_config* cfg);
 int64_t rae_exchange_floats(const rae_config* cfg);
 

@@ -216,9 +216,13 @@ inline int plan_resolve(const rae_config& c, const rae_buffers& buf, PlanSpec& s
     StepArgs& a = s.args;
     memset(&a, 0, sizeof(a));
     a.lay = plan_layout(c);
-    if ((int64_t)a.lay.rec * c.batch_size * c.world_size >= (1ll << 31) ||
-        (int64_t)3 * align4(c.embed) * c.batch_size * c.world_size >= (1ll << 31))
-        return fail(RAE_E_INVALID, "exchange buffer exceeds 2^31 floats (global batch too large)");
+    // 2^30 floats, not 2^31: RecBuf::load (rae_common.hpp) addresses a record through a raw
+    // buffer resource whose offsets are 32-bit BYTE offsets from the buffer's base, so a record
+    // at or beyond 4 GiB would wrap
+    if ((int64_t)a.lay.rec * c.batch_size * c.world_size >= (1ll << 30) ||
+        (int64_t)3 * align4(c.embed) * c.batch_size * c.world_size >= (1ll << 30))
+        return fail(RAE_E_INVALID, "exchange buffer exceeds 2^30 floats = 4 GiB, the range of its "
+                                   "32-bit byte offsets (global batch too large)");
     const int L = c.batch_size * c.world_size;
     const int NJ = 2 + 2 * c.neg_samples;
     a.dec = c.decoder;

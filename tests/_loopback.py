@@ -13,7 +13,8 @@ host staging, no process start per case.
              G-1 moves the bytes).  max_int answers with the bound the harness set and records
              what each rank asked with.
   Ranks      owns G ReconstructInducers / TrainEngines (rank 0 .. G-1, each with its own model
-             and optimizer, so its own parameter and accumulator replicas) and drives global
+             and optimizer, so its own parameter and accumulator replicas; the factory returns
+             either an inducer or a ready TrainEngine) and drives global
              batches for all of them in lockstep through the ABI's absolute-batch launches, in
              the order of TrainEngine._steps_eager.  The engines never call a collective from
              inside a step.
@@ -134,18 +135,21 @@ class Ranks:
     ReconstructInducer (world_size = G, that rank and exchange, graph_chunk = 1,
     index_overlap = False: no side stream), not yet compiled; kernel_forms is what those
     inducers are given (looked at only to refuse a peer-to-peer exchange before any plan
-    exists)."""
+    exists).  The factory may return a TrainEngine of the same description instead (a test that
+    builds its model from device tensors): inds is then empty."""
 
     def __init__(self, G, make_inducer, kernel_forms=None):
         refuse_p2p(kernel_forms)
         self.G = int(G)
         self.lb = Loopback(G)
-        self.inds = [make_inducer(k, self.lb.port(k)) for k in range(self.G)]
-        for ind in self.inds:
-            refuse_p2p(ind.kernel_forms)
+        made = [make_inducer(k, self.lb.port(k)) for k in range(self.G)]
+        for x in made:
+            refuse_p2p(x.kernel_forms)
+        self.inds = [x for x in made if hasattr(x, "compile_function")]
+        assert len(self.inds) in (0, self.G)
         for ind in self.inds:
             ind.compile_function()
-        self.engines = [ind.engine for ind in self.inds]
+        self.engines = [ind.engine for ind in self.inds] if self.inds else made
         e0 = self.engines[0]
         self.part = e0._dp
         assert all(e.world_size == self.G and e.dp_rank == k and e._dp == self.part and
@@ -158,6 +162,9 @@ class Ranks:
     def close(self):
         for ind in self.inds:
             ind._drop_engine()
+        if not self.inds:
+            for eng in self.engines:
+                eng.close()
 
     def set_negatives(self, negs):
         """negs[k]: rank k's (neg1, neg2), each (s, N) -- the same arrays on every rank."""

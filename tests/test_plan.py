@@ -28,8 +28,9 @@ def plan_dump(tmp_path_factory):
 def test_matrix_covers_every_rejection_and_form():
     """The fixture holds one config per rejection message of plan_resolve and both outcomes of
     every form the plan resolves.  ("update grid too large" has none: with the exchange buffer
-    below 2^31 floats and at most RAE_IDX_HMAX * RAE_IDX_PART records per table, update_grid
-    stays below 2048 + 1 + 2^20 / 17 + 6144 + 4 * 2^31 / 12 < 2^31.)"""
+    below 2^30 floats (4 GiB: the records' 32-bit byte offsets) and at most RAE_IDX_HMAX *
+    RAE_IDX_PART records per table, update_grid stays below 2048 + 1 + 2^20 / 17 + 6144 +
+    4 * 2^30 / 12 < 2^31.)"""
     src = open(os.path.join(ROOT, "relation-autoencoder_amd", "csrc", "rae_plan.hpp")).read()
     body = src[src.index("inline int plan_resolve("):]
     n_fail = body.count("return fail(")
