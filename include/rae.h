@@ -672,6 +672,50 @@ int rae_cluster_key_count(const int64_t* labels, const int32_t* keys, int64_t nr
 int rae_cluster_topk(const int32_t* counts, int32_t relations, int32_t n_keys, int64_t ld,
                      int32_t top, int32_t* keys_out, int32_t* counts_out, rae_stream_t stream);
 
+/* --- relation feature profiles: what the encoder's W keys on (no reference counterpart:
+ *     get_clusters_with_info dumps raw feature lists and is dead code) ---------------------- */
+/* Plan-free and stream-ordered like the entries above: every pointer is a device pointer except
+ * the struct itself, no allocation, no synchronisation (capturable), arguments checked before the
+ * first HIP call; they write only their outputs and the workspace.                          */
+
+/* support[f] (+)= the number of stored entries (i, f) of rows [row0, row0+nrows) whose value is
+ * non-zero (values NULL: every stored entry) -- np.bincount of the kept column indices.  Columns
+ * outside [0, n_features) are skipped and never read out of range.  Zeroed by a kernel first
+ * unless accumulate != 0.  Integer atomics only: exact whatever the grid or arrival order.
+ * 0 <= n_features < 2^31, 0 <= nrows < 2^31 (nrows == 0 still zeroes).  Pointers need their
+ * element alignment only.                                                                    */
+int rae_feature_support(const int32_t* indptr, const int32_t* indices, const float* values,
+                        int64_t n_features, int64_t row0, int64_t nrows, int32_t accumulate,
+                        int32_t* support, rae_stream_t stream);
+
+/* Per relation k the `top` best features by score(f, k), of the eligible features f in
+ * [0, n_features): support == NULL, or support[f] >= min_support.
+ *   centre == 0: score(f, k) = W[f * ldw + k];
+ *   centre == 1: score(f, k) = (float)((double)W[f, k] - s_f / (double)relations), one rounding to
+ *     fp32, s_f the row sum in double in rae_b3_metrics' order: lane j of 64 adds columns j,
+ *     j + 64, ... ascending, the 64 lane sums fold by the xor tree 32, 16, ..., 1.
+ * The candidates of relation k are the eligible f whose score is not NaN (-0.0f counts and is
+ * returned as +0.0f); row k of feats_out / scores_out ((relations, top)) is its candidates by
+ * score descending, then feature ascending (rae_topk_queries' total order: the output is unique),
+ * cut to `top` and padded with (-1, -inf).  1 <= relations <= 512 (no multiple-of-4 rule),
+ * 0 <= n_features < 2^31 (0: all padding; W may then be NULL), ldw >= relations, 1 <= top <= 32
+ * (top > n_features is valid); element offsets into W are 64-bit; W and support need their
+ * element alignment only.  A relation's row is bitwise independent of top's padding, of the
+ * launch decomposition and of the other relations.                                          */
+typedef struct rae_ftopk_args {
+    const float* W; int64_t n_features; int32_t relations; int64_t ldw;   /* ldw >= relations   */
+    const int32_t* support; int32_t min_support;  /* support NULL: every feature is eligible     */
+    int32_t centre;                               /* 0: W[f,k]   1: W[f,k] - mean_f              */
+    int32_t top;                                  /* 1..32                                       */
+    int32_t* feats_out; float* scores_out;        /* (relations, top); scores_out may be NULL    */
+    void* workspace; int64_t workspace_bytes;     /* 256-byte aligned                            */
+} rae_ftopk_args;
+/* The bytes rae_feature_topk needs for a's n_features, relations, top and centre: the strips'
+ * lists (at most 128 strips x relations x top keys of 8 bytes) plus, centred, 8 bytes per
+ * feature.  Host only; -1 on a bad argument.                                                */
+int64_t rae_feature_topk_workspace_bytes(const rae_ftopk_args* a);
+int rae_feature_topk(const rae_ftopk_args* a, rae_stream_t stream);
+
 /* --- measurement helper (bench.py; no reference counterpart) ------------------------- */
 /* STREAM-style device copy of `bytes` (multiple of 16, 16-byte aligned pointers) with float4
  * loads and stores: the measured HBM ceiling bench.py reports next to the 8 TB/s spec.   */

@@ -37,6 +37,7 @@
 #include "rae_rank.hpp"
 #include "rae_relscore.hpp"
 #include "rae_topk.hpp"
+#include "rae_feature.hpp"
 #include "rae_sampler.hpp"
 #include "rae_sp.hpp"
 #include "rae_step.hpp"
@@ -2292,6 +2293,111 @@ extern "C" int rae_cluster_topk(const int32_t* counts, int32_t relations, int32_
     hipLaunchKernelGGL(k_ctopk, dim3((unsigned)relations), dim3(RAE_TK_BT), 0, (hipStream_t)stream,
                        (const int*)counts, (int)n_keys, (long long)ld, (int)top, keys_out,
                        counts_out);
+    HIPCHK(hipGetLastError());
+    return RAE_OK;
+}
+
+// ---- relation feature profiles (rae_feature.hpp) ----------------------------------------------
+extern "C" int rae_feature_support(const int32_t* indptr, const int32_t* indices,
+                                   const float* values, int64_t n_features, int64_t row0,
+                                   int64_t nrows, int32_t accumulate, int32_t* support,
+                                   rae_stream_t stream) {
+    if (!indptr) return fail(RAE_E_INVALID, "indptr is NULL");
+    if (!indices) return fail(RAE_E_INVALID, "indices is NULL");
+    if (!support) return fail(RAE_E_INVALID, "support is NULL");
+    if (n_features < 0 || n_features >= (1ll << 31))
+        return fail(RAE_E_INVALID, "n_features must be in [0, 2^31)");
+    if (row0 < 0) return fail(RAE_E_INVALID, "row0 must be >= 0");
+    if (nrows < 0 || nrows >= (1ll << 31)) return fail(RAE_E_INVALID, "nrows must be in [0, 2^31)");
+    if (((uintptr_t)indptr & 3) || ((uintptr_t)indices & 3) || ((uintptr_t)values & 3) ||
+        ((uintptr_t)support & 3))
+        return fail(RAE_E_INVALID, "indptr / indices / values / support must be 4-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    unsigned* sp = (unsigned*)support;
+    if (n_features == 0) return RAE_OK;       // no cell to zero or count
+    if (!accumulate) {
+        const int64_t zg = std::min<int64_t>((n_features + 255) / 256, 4096);
+        hipLaunchKernelGGL(k_ck_zero, dim3((unsigned)zg), dim3(256), 0, st, sp, (long long)n_features);
+        HIPCHK(hipGetLastError());
+    }
+    if (nrows == 0) return RAE_OK;
+    const int64_t grid = std::max<int64_t>(1, std::min<int64_t>(ceil_div(nrows, (int64_t)RAE_FS_ROWS),
+                                                                RAE_FS_GRID));
+    // values by 16-byte loads when they are aligned where the indices are
+    const int vm = !values ? 0 : ((((uintptr_t)values ^ (uintptr_t)indices) & 15) == 0 ? 1 : 2);
+    const dim3 g((unsigned)grid), b(RAE_FS_BT);
+    if (vm == 0)
+        hipLaunchKernelGGL(k_fsupport<0>, g, b, 0, st, indptr, indices, values,
+                           (long long)n_features, (long long)row0, (long long)nrows, sp);
+    else if (vm == 1)
+        hipLaunchKernelGGL(k_fsupport<1>, g, b, 0, st, indptr, indices, values,
+                           (long long)n_features, (long long)row0, (long long)nrows, sp);
+    else
+        hipLaunchKernelGGL(k_fsupport<2>, g, b, 0, st, indptr, indices, values,
+                           (long long)n_features, (long long)row0, (long long)nrows, sp);
+    HIPCHK(hipGetLastError());
+    return RAE_OK;
+}
+
+namespace {
+struct FtopkLayout { size_t o_keys, o_mean, total; int strips; };
+// shapes of rae_feature_topk and its workspace layout (host only)
+int ftopk_layout(const rae_ftopk_args* a, FtopkLayout& L) {
+    if (!a) return fail(RAE_E_INVALID, "null argument");
+    if (a->relations < 1 || a->relations > 512)
+        return fail(RAE_E_INVALID, "relations must be in [1, 512]");
+    if (a->n_features < 0 || a->n_features >= (1ll << 31))
+        return fail(RAE_E_INVALID, "n_features must be in [0, 2^31)");
+    if (a->ldw < a->relations) return fail(RAE_E_INVALID, "ldw is smaller than relations");
+    if (const int rc = topk_top(a->top)) return rc;
+    if (a->centre != 0 && a->centre != 1) return fail(RAE_E_INVALID, "centre must be 0 or 1");
+    L.strips = ftopk_strips(a->n_features);
+    L.o_keys = 0;
+    L.o_mean = ev_align((size_t)L.strips * (size_t)a->relations * (size_t)a->top * sizeof(rae_key64));
+    L.total = L.o_mean + (a->centre ? ev_align((size_t)a->n_features * sizeof(double)) : 0);
+    return RAE_OK;
+}
+}  // namespace
+
+extern "C" int64_t rae_feature_topk_workspace_bytes(const rae_ftopk_args* a) {
+    FtopkLayout L;
+    if (ftopk_layout(a, L)) return -1;
+    return (int64_t)L.total;
+}
+
+extern "C" int rae_feature_topk(const rae_ftopk_args* a, rae_stream_t stream) {
+    FtopkLayout L;
+    if (const int rc = ftopk_layout(a, L)) return rc;
+    if (a->n_features > 0 && !a->W) return fail(RAE_E_INVALID, "W is NULL");
+    if (!a->feats_out) return fail(RAE_E_INVALID, "feats_out is NULL");
+    if (((uintptr_t)a->W & 3) || ((uintptr_t)a->support & 3) || ((uintptr_t)a->feats_out & 3) ||
+        ((uintptr_t)a->scores_out & 3))
+        return fail(RAE_E_INVALID, "W / support / feats_out / scores_out must be 4-byte aligned");
+    if (const int rc = check_workspace(a->workspace, a->workspace_bytes, L.total,
+                                       "rae_feature_topk_workspace_bytes"))
+        return rc;
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)a->workspace;
+    FtopkArgs k;
+    k.W = a->W; k.d = a->n_features; k.ldw = a->ldw; k.strip_rows = ftopk_strip_rows(a->n_features);
+    k.m = a->relations; k.top = a->top; k.min_support = a->min_support;
+    k.support = a->centre ? nullptr : a->support;
+    k.mean = a->centre ? (const double*)(ws + L.o_mean) : nullptr;
+    k.keys = (rae_key64*)(ws + L.o_keys);
+    if (a->centre && a->n_features > 0) {
+        const int64_t per = (int64_t)(RAE_FR_BT / 64) * RAE_FR_ROWS;
+        const int64_t gr = std::min<int64_t>(ceil_div(a->n_features, per), RAE_FR_GRID);
+        hipLaunchKernelGGL(k_frowstat, dim3((unsigned)gr), dim3(RAE_FR_BT), 0, st, a->W,
+                           (long long)a->n_features, (int)a->relations, (long long)a->ldw,
+                           a->support, (int)a->min_support, (double*)(ws + L.o_mean));
+    }
+    const dim3 grid((unsigned)ceil_div((int)a->relations, 64), (unsigned)L.strips);
+    with_bool(a->centre != 0, [&](auto Cf) {
+        hipLaunchKernelGGL(k_ftopk<RAE_CV(Cf)>, grid, dim3(RAE_FT_BT), 0, st, k);
+    });
+    hipLaunchKernelGGL(k_ftopk_finish, dim3((unsigned)ceil_div((int)a->relations, RAE_FT_FQ)),
+                       dim3(RAE_FT_FQ * 64), 0, st, (const rae_key64*)k.keys, L.strips,
+                       (int)a->relations, (int)a->top, a->feats_out, a->scores_out);
     HIPCHK(hipGetLastError());
     return RAE_OK;
 }

@@ -85,6 +85,7 @@ EXPORTS = (
     "rae_relation_scores", "rae_eval_relations", "rae_relscore_workspace_bytes",
     "rae_cluster_count", "rae_b3_metrics",
     "rae_row_keys", "rae_cluster_key_count", "rae_cluster_topk",
+    "rae_feature_support", "rae_feature_topk", "rae_feature_topk_workspace_bytes",
 )
 RAE_IPC_HANDLE_BYTES = 64
 # rae_index_dims' values in order, and rae_index_read's regions (include/rae.h RAE_IDXR_*)
@@ -230,6 +231,31 @@ def relscore_block_examples(relations: int) -> int:
     return 128 if relations <= 16 else 64
 
 
+class RaeFtopkArgs(C.Structure):
+    """rae_ftopk_args (include/rae.h): the `top` best features of every relation by W."""
+    _fields_ = [
+        ("W", _P), ("n_features", C.c_int64), ("relations", C.c_int32), ("ldw", C.c_int64),
+        ("support", _P), ("min_support", C.c_int32), ("centre", C.c_int32), ("top", C.c_int32),
+        ("feats_out", _P), ("scores_out", _P),
+        ("workspace", _P), ("workspace_bytes", C.c_int64),
+    ]
+
+
+# rae_feature_topk: largest `top` and the selection kernel's decomposition (csrc/rae_feature.hpp
+# RAE_FT_*): row phases per workgroup, rows of a phase in flight, shortest strip, most strips
+RAE_FT_MAXTOP, RAE_FT_WAVES, RAE_FT_U, RAE_FT_STRIP_ROWS, RAE_FT_MAXSTRIPS = 32, 8, 8, 512, 128
+
+
+def ftopk_strips(d: int) -> int:
+    """The strips rae_feature_topk cuts d features into (csrc/rae_feature.hpp ftopk_strips)."""
+    return max(1, min(RAE_FT_MAXSTRIPS, -(-int(d) // RAE_FT_STRIP_ROWS)))
+
+
+def ftopk_strip_rows(d: int) -> int:
+    step = RAE_FT_WAVES * RAE_FT_U
+    return -(-(-(-int(d) // ftopk_strips(d))) // step) * step
+
+
 LABEL_MODES = ("encoder", "decoder", "joint")
 
 
@@ -340,6 +366,13 @@ def load(path: str | None = None):
     lib.rae_cluster_key_count.restype = C.c_int
     lib.rae_cluster_topk.argtypes = [_P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _P, _P, _P]
     lib.rae_cluster_topk.restype = C.c_int
+    lib.rae_feature_support.argtypes = [_P, _P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
+                                        _P, _P]
+    lib.rae_feature_support.restype = C.c_int
+    lib.rae_feature_topk_workspace_bytes.argtypes = [C.POINTER(RaeFtopkArgs)]
+    lib.rae_feature_topk_workspace_bytes.restype = C.c_int64
+    lib.rae_feature_topk.argtypes = [C.POINTER(RaeFtopkArgs), _P]
+    lib.rae_feature_topk.restype = C.c_int
     lib.rae_neg_sample.argtypes = [_P, C.c_int64, _P, C.c_int64, _P, _P]
     lib.rae_neg_sample_philox.argtypes = [_P, C.c_int64, C.c_uint64, C.c_uint64, C.c_int64, _P, _P]
     lib.rae_time_next.argtypes = [_P, _P, _P]

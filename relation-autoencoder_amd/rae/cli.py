@@ -83,6 +83,17 @@ def get_command_args(argv=None, program_name="rae"):
                    help="after each evaluation print every induced relation's N (default 5, "
                         "1..32) highest-scoring entities per argument slot with their scores "
                         "(sp and rescal+sp)")
+    p.add_argument("--print-features", dest="print_features", type=int, nargs="?",
+                   const=10, default=0, metavar="N",
+                   help="after each evaluation print every induced relation's N (default 10, "
+                        "1..32) features with the highest row-centred encoder weight, with "
+                        "that weight and the feature's count in the training split")
+    p.add_argument("--print-features-min-count", dest="print_features_min_count", type=int,
+                   default=5, metavar="C",
+                   help="--print-features ranks only features in at least C training rows "
+                        "(a rare feature carries a large, meaningless weight)")
+    p.add_argument("--print-features-raw", dest="print_features_raw", action="store_true",
+                   help="--print-features ranks by W[f, k] itself, not the row-centred weight")
     p.add_argument("--predict-arguments", dest="predict_arguments", type=int, default=0,
                    metavar="ROWS",
                    help="after the last epoch print the model's top predictions for both "
@@ -189,7 +200,10 @@ def main(argv=None):
                              predict_arguments=args.predict_arguments,
                              predict_top=args.predict_top,
                              label_with=args.label_with,
-                             predict_relations=args.predict_relations)
+                             predict_relations=args.predict_relations,
+                             print_features=args.print_features,
+                             print_features_min_count=args.print_features_min_count,
+                             print_features_raw=args.print_features_raw)
     if exchange is not None:
         ind.compile_function()
         rdist.warm_up(exchange, ind.engine.exchange_buf)

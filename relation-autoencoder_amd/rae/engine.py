@@ -1448,3 +1448,55 @@ class TrainEngine:
         f1, pre, rec, nel = (float(x) for x in host[:4].view(np.float64))
         return (ClusterResult(f1, pre, rec, int(nel), host[4:].copy(), None),
                 self._profile_result(int(top)))
+
+    # ------------------------------------------------------------------ relation feature profiles
+    def feature_support(self, split: DeviceSplit):
+        """support[f] of `split` in HBM (int32, max(split.d, 1) words): the number of its rows
+        that store a non-zero value in column f (rae_feature_support over the whole split) --
+        once per split, cached like _keys_dev: the support is static."""
+        cache = self.__dict__.setdefault("_support_cache", {})
+        hit = cache.get(id(split))
+        if hit is not None and hit[0] is split:
+            return hit[1]
+        sup = torch.zeros(max(split.d, 1), dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.rae_feature_support(
+            C.c_void_p(split.indptr.data_ptr()), C.c_void_p(split.indices.data_ptr()),
+            C.c_void_p(split.values.data_ptr()) if split.values is not None else None,
+            split.d, 0, split.N, 0, C.c_void_p(sup.data_ptr()), self._stream()),
+            "rae_feature_support")
+        cache[id(split)] = (split, sup)
+        return sup
+
+    def relation_features(self, top: int = 10, centre: bool = True, min_support: int = 0,
+                          split: DeviceSplit | None = None):
+        """What the encoder keys on: per induced relation k the `top` features f with the highest
+        weight W[f, k] -- centre: the row-centred weight W[f, k] - mean_k' W[f, k'], the
+        identifiable one (softmax ignores a constant added to a row of W) -- among the features
+        with at least min_support rows in `split` (None: no filter).  rae_feature_topk: returns
+        (feats int32, scores fp32), both (m, top), score descending then feature ascending,
+        padded with (-1, -inf); rae.evaluation.feature_topk is the host oracle.  Queued on the
+        current stream, no host synchronisation.  Touches no parameter, accumulator, plan state,
+        cursor, negative or RNG; partitioned update with stale rows: gathers W first (a
+        collective, like label)."""
+        top = self._check_top(top)
+        if self.stale(accumulators=False):
+            self.sync_replicas(accumulators=False)
+        W = self.model.params[0]
+        d = int(W.shape[0])
+        sup = None
+        if split is not None:
+            if split.d != d:
+                raise ValueError(f"split over {split.d} features, W has {d}")
+            sup = self.feature_support(split)
+        feats = torch.empty((self.m, top), dtype=torch.int32, device=self.device)
+        scores = torch.empty((self.m, top), dtype=torch.float32, device=self.device)
+        a = _lib.RaeFtopkArgs()
+        a.W, a.n_features, a.relations, a.ldw = _lib.ptr(W), d, self.m, int(W.stride(0))
+        a.support, a.min_support = _lib.ptr(sup), int(min_support)
+        a.centre, a.top = 1, _lib.RAE_FT_MAXTOP         # the workspace: sized for every call
+        self._workspace(a, "_ftopk_ws", "rae_feature_topk_workspace_bytes",
+                        lambda: self.lib.rae_feature_topk_workspace_bytes(C.byref(a)))
+        a.centre, a.top = int(bool(centre)), top
+        a.feats_out, a.scores_out = _lib.ptr(feats), _lib.ptr(scores)
+        _lib.check(self.lib.rae_feature_topk(C.byref(a), self._stream()), "rae_feature_topk")
+        return feats, scores

@@ -386,6 +386,97 @@ def format_relation_preferences(ents, scores, names=None):
     return lines
 
 
+# ------------------------------------------------------------------ relation feature profiles
+def feature_support(X, use_values=True, n_features=None):
+    """The host oracle of rae_feature_support: int32 per feature, the number of stored entries of
+    the CSR matrix X in its column whose value is non-zero -- the feature's document frequency.
+    use_values=False counts every stored entry (values == NULL).  Columns outside
+    [0, n_features) (default: X's width) are skipped."""
+    d = int(X.shape[1] if n_features is None else n_features)
+    idx = np.asarray(X.indices, dtype=np.int64)
+    keep = (idx >= 0) & (idx < d)
+    if use_values:
+        keep &= np.asarray(X.data) != 0
+    return np.bincount(idx[keep], minlength=d).astype(np.int32)[:d]
+
+
+def tree_row_sum(W):
+    """The row sums of W (d, m) in float64 in the order rae_b3_metrics and rae_feature_topk use:
+    lane j of 64 adds columns j, j + 64, ... in ascending order from 0.0, then the 64 lane sums
+    fold by the xor tree 32, 16, ..., 1 (every lane adds its partner's value).  A function of m
+    alone; bit for bit the device's."""
+    W = np.asarray(W)
+    if W.ndim != 2:
+        raise ValueError("W must be (d, m)")
+    d, m = W.shape
+    lanes = np.zeros((d, 64), dtype=np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for c0 in range(0, m, 64):
+            w = min(64, m - c0)
+            lanes[:, :w] = lanes[:, :w] + W[:, c0:c0 + w].astype(np.float64)
+        idx = np.arange(64)
+        for o in (32, 16, 8, 4, 2, 1):
+            lanes = lanes + lanes[:, idx ^ o]
+    return lanes[:, 0].copy()
+
+
+def feature_scores(W, centre=True):
+    """score(f, k) of rae_feature_topk, float32 (d, m): W itself, or centred
+    (float)((double)W[f, k] - tree_row_sum(W)[f] / m) with one rounding to float32."""
+    W = np.asarray(W, dtype=np.float32)
+    if not centre:
+        return W.copy()
+    with np.errstate(invalid="ignore", over="ignore"):
+        mean = tree_row_sum(W) / np.float64(W.shape[1])
+        return (W.astype(np.float64) - mean[:, None]).astype(np.float32)
+
+
+def feature_topk(W, support=None, min_support=0, centre=True, top=10):
+    """The host oracle of rae_feature_topk: (feats int32, scores float32), both (m, top).  Row k:
+    the features f with support[f] >= min_support (support None: all) whose score is not NaN,
+    by score descending, then feature ascending, cut to `top` and padded with (-1, -inf).
+    -0.0 is +0.0, in the order and in the output."""
+    W = np.asarray(W, dtype=np.float32)
+    d, m = W.shape
+    s = feature_scores(W, centre)
+    s = np.where(s == 0, np.float32(0), s)                    # -0 -> +0
+    ok = np.ones(d, dtype=bool) if support is None else \
+        np.asarray(support)[:d].astype(np.int64) >= int(min_support)
+    feats = np.full((m, top), -1, dtype=np.int32)
+    scores = np.full((m, top), -np.inf, dtype=np.float32)
+    for k in range(m):
+        col = s[:, k]
+        cand = np.flatnonzero(ok & ~np.isnan(col))
+        order = cand[np.lexsort((cand, -col[cand]))][:top]
+        feats[k, :order.shape[0]] = order
+        scores[k, :order.shape[0]] = col[order]
+    return feats, scores
+
+
+def format_relation_features(feats, scores, support, names=None):
+    """feats / scores (m, top) of TrainEngine.relation_features -> one line per relation:
+    'relation k: name:score(count) ...', best first.  name is names(f) of a callable or names[f]
+    of a mapping / sequence (the lexicon's pruned strings), the feature id where there is none;
+    count is support[f] (support None: no count).  Padding is not printed."""
+    feats, scores = np.asarray(feats), np.asarray(scores)
+    lines = []
+    for k in range(feats.shape[0]):
+        items = []
+        for f, s in zip(feats[k], scores[k]):
+            if f < 0:
+                continue
+            name = None
+            if callable(names):
+                name = names(int(f))
+            elif names is not None:
+                name = entity_name(names, f)
+            name = str(int(f)) if name is None else str(name)
+            cnt = "" if support is None else "({})".format(int(support[int(f)]))
+            items.append("{}:{:.9g}{}".format(name, float(s), cnt))      # %.9g round-trips a float32
+        lines.append("relation {}: {}".format(k, " ".join(items)).rstrip())
+    return lines
+
+
 # ------------------------------------------------------------------ relation scores from the decoder
 def relation_scores(params, decoder, e1, e2):
     """psi (nq, m) float64, the oracle of rae_relation_scores: the decoder's score of every

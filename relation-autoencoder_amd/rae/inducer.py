@@ -15,7 +15,8 @@ from .data import SPLIT_LABELS
 from .engine import DeviceSplit, TrainEngine
 from .evaluation import (GoldIndex, KeyIndex, construct_split_evaluator,
                          format_argument_predictions, format_cluster_profiles,
-                         format_relation_predictions, format_relation_preferences, key_table, row_keys, topk_from_table)
+                         format_relation_features, format_relation_predictions,
+                         format_relation_preferences, key_table, row_keys, topk_from_table)
 from .model import OieModelFunctions, _as_bool, make_optimizer
 from .negatives import NegativeExampleGenerator
 
@@ -79,11 +80,16 @@ class ReconstructInducer:
                  eval_cost=False, eval_seed=None, cluster_eval="host", print_clusters="off",
                  print_top=5, print_by="trigger", eval_rank=False, eval_rank_ks=(1, 10, 100),
                  eval_rank_rows=None, print_preferences=0, predict_arguments=0, predict_top=10,
-                 label_with="encoder", predict_relations=0):
+                 label_with="encoder", predict_relations=0, print_features=0,
+                 print_features_min_count=5, print_features_raw=False):
         if label_with not in ("encoder", "decoder", "joint"):
             raise ValueError("label_with must be 'encoder', 'decoder' or 'joint'")
         if int(predict_relations) < 0:
             raise ValueError("predict_relations must be >= 0")
+        if not 0 <= int(print_features) <= 32:
+            raise ValueError("print_features must be in [0, 32] (0: off)")
+        if int(print_features_min_count) < 0:
+            raise ValueError("print_features_min_count must be >= 0")
         if not 0 <= int(print_preferences) <= 32:
             raise ValueError("print_preferences must be in [0, 32] (0: off)")
         if int(predict_arguments) < 0 or not 1 <= int(predict_top) <= 32:
@@ -171,6 +177,13 @@ class ReconstructInducer:
         # label (TrainEngine.eval_relations)
         self.label_with = label_with
         self.predict_relations = int(predict_relations)
+        # print_features: after each epoch's evaluation learn() prints, per induced relation, the
+        # N features the encoder weighs highest for it among those in at least
+        # print_features_min_count training rows, with their row-centred weight
+        # (print_features_raw: W[f, k] itself) and that count (TrainEngine.relation_features)
+        self.print_features = int(print_features)
+        self.print_features_min_count = int(print_features_min_count)
+        self.print_features_raw = bool(print_features_raw)
         # cluster_eval: where learn() scores the induced clusters -- "host": the label download
         # and the Python sets of the reference (get_clusters_sets + SingleLabelClusterEvaluation);
         # "device": the contingency table and B^3 on the GPU (TrainEngine.cluster_metrics), same
@@ -354,6 +367,10 @@ class ReconstructInducer:
                 lines = self.relation_preference_lines()
                 if verbose:
                     print("\n".join(lines))
+            if self.print_features:
+                lines = self.relation_feature_lines()
+                if verbose:
+                    print("\n".join(lines))
         if self.predict_arguments:
             for split in (SPLIT_LABELS[:1] if self._mode() == 1 else SPLIT_LABELS[1:]):
                 lines = self.argument_prediction_lines(split)
@@ -373,6 +390,22 @@ class ReconstructInducer:
         ents, scores = self.engine.relation_preferences(self.print_preferences or 5)
         return format_relation_preferences(ents.cpu().numpy(), scores.cpu().numpy(),
                                            getattr(self.data, "id2Arg", None))
+
+    def relation_feature_lines(self):
+        """print_features' lines at the current parameters: one per relation, the features' names
+        from the dataset's lexicon when it has one (the feature ids otherwise), the counts the
+        train split's."""
+        if not self._check_for_compiled_functions():
+            self.compile_function()
+        eng = self.engine
+        feats, scores = eng.relation_features(self.print_features or 10,
+                                              centre=not self.print_features_raw,
+                                              min_support=self.print_features_min_count,
+                                              split=eng.split)
+        lex = getattr(self.data, "featureLex", None)
+        return format_relation_features(feats.cpu().numpy(), scores.cpu().numpy(),
+                                        eng.feature_support(eng.split).cpu().numpy(),
+                                        lex.get_str_pruned if lex is not None else None)
 
     def argument_prediction_lines(self, split):
         """predict_arguments' lines for the first predict_arguments rows of `split`: a header,
