@@ -339,7 +339,8 @@ def size_specs():
     return out
 
 
-def main(outfile=OUT):
+def record(outfile, cases, run, size_specs, size_case, size_ok):
+    """Build the tree, make every call and write the table (gen_analysis_rejections.py shares it)."""
     sys.path.insert(0, ROOT)
     import torch
     assert not torch.cuda.is_available(), "made-up addresses: run this where no GPU is visible"
@@ -347,13 +348,13 @@ def main(outfile=OUT):
     ge.build()
     lib = _lib_mod().load()
     rej, sizes = [], []
-    for c in cases():
+    for c in cases:
         rc, msg = run(lib, c)
         assert rc == INVALID and msg, (c, rc, msg)
         rej.append(dict(c, rc=rc, msg=msg))
-    for s in size_specs():
+    for s in size_specs:
         b = size_case(lib, s)
-        assert b >= 0 and (b > 0 or s["fn"] == SIZERS[3] and s["form"] == "q"), (s, b)
+        assert size_ok(s, b), (s, b)
         sizes.append(dict(s, bytes=b))
     with open(outfile, "w") as fh:             # one case per line
         fh.write('{"rejections": [\n')
@@ -362,6 +363,11 @@ def main(outfile=OUT):
         fh.write(",\n".join(json.dumps(s) for s in sizes))
         fh.write("\n]}\n")
     print(f"wrote {outfile}: {len(rej)} refused cases, {len(sizes)} sizes")
+
+
+def main(outfile=OUT):
+    record(outfile, cases(), run, size_specs(), size_case,
+           lambda s, b: b >= 0 and (b > 0 or s["fn"] == SIZERS[3] and s["form"] == "q"))
 
 
 if __name__ == "__main__":

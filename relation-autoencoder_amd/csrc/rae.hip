@@ -20,6 +20,7 @@
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <type_traits>
 
@@ -694,6 +695,11 @@ template <class F> static void with_q(int q, F&& f) {          // row slots per 
 template <class F> static void with_opt(int opt, F&& f) {      // RAE_OPT_ADAGRAD 0 / RAE_OPT_SGD 1
     if (opt == RAE_OPT_ADAGRAD) f(std::integral_constant<int, 0>{});
     else f(std::integral_constant<int, 1>{});
+}
+template <class F> static void with_vm(int vm, F&& f) {        // k_fsupport's values mode: 0, 1 or 2
+    if (vm == 0) f(std::integral_constant<int, 0>{});
+    else if (vm == 1) f(std::integral_constant<int, 1>{});
+    else f(std::integral_constant<int, 2>{});
 }
 
 extern "C" const char* rae_last_error(void) { return g_last_error.c_str(); }
@@ -1482,8 +1488,30 @@ extern "C" int rae_label(const int32_t* indptr, const int32_t* indices, const fl
 namespace {
 inline size_t ev_align(size_t x) { return (x + 255) & ~(size_t)255; }
 
-int entity_count(int64_t n) {
-    if (n < 1 || n >= (1ll << 31)) return fail(RAE_E_INVALID, "n_entities must be in [1, 2^31)");
+// the argument checks the entries share; each fails with the text its entry always had
+int count_range(const char* name, int64_t v, int64_t lo) {    // lo <= v < 2^31
+    if (v < lo || v >= (1ll << 31))
+        return fail(RAE_E_INVALID, std::string(name) + " must be in [" + std::to_string(lo) + ", 2^31)");
+    return RAE_OK;
+}
+int entity_count(int64_t n) { return count_range("n_entities", n, 1); }
+int relations_range(int m) {
+    if (m < 1 || m > 512) return fail(RAE_E_INVALID, "relations must be in [1, 512]");
+    return RAE_OK;
+}
+int key_count(int n_keys) {
+    if (n_keys < 1 || n_keys > (1 << 22)) return fail(RAE_E_INVALID, "n_keys must be in [1, 2^22]");
+    return RAE_OK;
+}
+struct NamedPtr { const void* p; const char* name; };
+int not_null(std::initializer_list<NamedPtr> ps) {            // the first NULL one, in list order
+    for (const NamedPtr& n : ps)
+        if (!n.p) return fail(RAE_E_INVALID, std::string(n.name) + " is NULL");
+    return RAE_OK;
+}
+int aligned(std::initializer_list<const void*> ps, uintptr_t mask, const char* msg) {
+    for (const void* p : ps)
+        if ((uintptr_t)p & mask) return fail(RAE_E_INVALID, msg);
     return RAE_OK;
 }
 // shapes of the caller-given-queries entries (rae_rank_queries, rae_topk_queries)
@@ -1495,7 +1523,7 @@ int query_shapes(int embed, int64_t n_entities) {
 // between them)
 int model_shapes(int dec, int m, int r) {
     if (dec < 0 || dec > 2) return fail(RAE_E_INVALID, "decoder must be 0..2");
-    if (m < 1 || m > 512) return fail(RAE_E_INVALID, "relations must be in [1, 512]");
+    if (const int rc = relations_range(m)) return rc;
     if ((m % 4) != 0 && m > 128)
         return fail(RAE_E_INVALID, "relations must be a multiple of 4 above 128");
     if (r < 1 || r > 1024) return fail(RAE_E_INVALID, "embed must be in [1, 1024]");
@@ -2121,23 +2149,45 @@ extern "C" int rae_eval_relations(const rae_eval_args* a, const rae_rel_out* out
     return RAE_OK;
 }
 
-// ---- cluster evaluation ---------------------------------------------------------------------
+// ---- cluster evaluation and profiles: what their entries share (host only) ---------------------
+namespace {
+// p[0, n) = 0 on the stream unless the entry accumulates; at most `cap` workgroups
+template <class T> int zero_unless(bool accumulate, T* p, int64_t n, int64_t cap, hipStream_t st) {
+    if (accumulate) return RAE_OK;
+    const int64_t zg = std::min<int64_t>((n + 255) / 256, cap);
+    hipLaunchKernelGGL(k_zero<T>, dim3((unsigned)zg), dim3(256), 0, st, p, (long long)n);
+    HIPCHK(hipGetLastError());
+    return RAE_OK;
+}
+// row_pair_stream's head: the rows before the first index at which both pointers are 16-byte
+// aligned (*gv); with none, the labels alone are aligned and `second` is read as dwords
+int pair_head(const int64_t* labels, const int32_t* second, int64_t nrows, bool* gv) {
+    int head = -1;
+    for (int h = 0; h < 4; ++h)
+        if ((((uintptr_t)(labels + h)) & 15) == 0 && (((uintptr_t)(second + h)) & 15) == 0) {
+            head = h;
+            break;
+        }
+    *gv = head >= 0;
+    if (!*gv) head = ((uintptr_t)labels & 15) ? 1 : 0;
+    return head > nrows ? (int)nrows : head;
+}
+}  // namespace
+
 extern "C" int rae_cluster_count(const int64_t* labels, const int32_t* gold, int64_t nrows,
                                  int32_t relations, int32_t n_gold, int32_t form, int64_t* table,
                                  rae_stream_t stream) {
-    if (!labels) return fail(RAE_E_INVALID, "labels is NULL");
-    if (!gold) return fail(RAE_E_INVALID, "gold is NULL");
-    if (!table) return fail(RAE_E_INVALID, "table is NULL");
-    if (relations < 1 || relations > 512)
-        return fail(RAE_E_INVALID, "relations must be in [1, 512]");
+    if (const int rc = not_null({{labels, "labels"}, {gold, "gold"}, {table, "table"}})) return rc;
+    if (const int rc = relations_range(relations)) return rc;
     if (n_gold < 0 || n_gold > 4095) return fail(RAE_E_INVALID, "n_gold must be in [0, 4095]");
     if (nrows < 0) return fail(RAE_E_INVALID, "nrows must be >= 0");
     const bool accumulate = (form & RAE_CCOUNT_ACCUMULATE) != 0;
     const int kind = form & ~RAE_CCOUNT_ACCUMULATE;
     if (kind != RAE_CCOUNT_AUTO && kind != RAE_CCOUNT_LDS && kind != RAE_CCOUNT_GLOBAL)
         return fail(RAE_E_INVALID, "form must be RAE_CCOUNT_AUTO, _LDS or _GLOBAL");
-    if (((uintptr_t)labels & 7) || ((uintptr_t)gold & 3) || ((uintptr_t)table & 7))
-        return fail(RAE_E_INVALID, "labels / gold / table must be aligned to their element size");
+    const char* al = "labels / gold / table must be aligned to their element size";
+    if (const int rc = aligned({labels, table}, 7, al)) return rc;
+    if (const int rc = aligned({gold}, 3, al)) return rc;
     const int64_t cells = (int64_t)relations * (n_gold + 1);
     // a workgroup's 32-bit counters hold its share of the rows: nrows / 512 workgroups < 2^31
     const bool fits = cells <= RAE_CC_LDS_CELLS && nrows < (1ll << 40);
@@ -2147,23 +2197,10 @@ extern "C" int rae_cluster_count(const int64_t* labels, const int32_t* gold, int
     const bool lds = kind == RAE_CCOUNT_LDS || (kind == RAE_CCOUNT_AUTO && fits);
     hipStream_t st = (hipStream_t)stream;
     unsigned long long* tb = (unsigned long long*)table;
-    if (!accumulate) {
-        const int64_t zg = std::min<int64_t>((cells + 255) / 256, 1024);
-        hipLaunchKernelGGL(k_cc_zero, dim3((unsigned)zg), dim3(256), 0, st, tb, (long long)cells);
-        HIPCHK(hipGetLastError());
-    }
+    if (const int rc = zero_unless(accumulate, tb, cells, 1024, st)) return rc;
     if (nrows == 0) return RAE_OK;
-    // rows before the first index at which both pointers are 16-byte aligned (GV); with none,
-    // the labels alone are aligned and the gold ids are read as dwords
-    int head = -1;
-    for (int h = 0; h < 4; ++h)
-        if ((((uintptr_t)(labels + h)) & 15) == 0 && (((uintptr_t)(gold + h)) & 15) == 0) {
-            head = h;
-            break;
-        }
-    const bool gv = head >= 0;
-    if (!gv) head = ((uintptr_t)labels & 15) ? 1 : 0;
-    if (head > nrows) head = (int)nrows;
+    bool gv;
+    const int head = pair_head(labels, gold, nrows, &gv);
     const int64_t nq = (nrows - head) >> 2;
     const int64_t per = (int64_t)RAE_CC_BT * RAE_CC_QPT;
     int64_t grid = (nq + per - 1) / per;
@@ -2189,16 +2226,14 @@ extern "C" int rae_cluster_count(const int64_t* labels, const int32_t* gold, int
 extern "C" int rae_b3_metrics(const int64_t* table, const int64_t* gold_sizes, int64_t n_assessable,
                               int32_t relations, int32_t n_gold, double* metrics_out,
                               int64_t* sizes_out, rae_stream_t stream) {
-    if (!table) return fail(RAE_E_INVALID, "table is NULL");
-    if (!metrics_out) return fail(RAE_E_INVALID, "metrics_out is NULL");
-    if (relations < 1 || relations > 512)
-        return fail(RAE_E_INVALID, "relations must be in [1, 512]");
+    if (const int rc = not_null({{table, "table"}, {metrics_out, "metrics_out"}})) return rc;
+    if (const int rc = relations_range(relations)) return rc;
     if (n_gold < 0 || n_gold > 4095) return fail(RAE_E_INVALID, "n_gold must be in [0, 4095]");
     if (n_gold > 0 && !gold_sizes) return fail(RAE_E_INVALID, "gold_sizes is NULL");
     if (n_assessable < 0) return fail(RAE_E_INVALID, "n_assessable must be >= 0");
-    if (((uintptr_t)table & 7) || ((uintptr_t)gold_sizes & 7) || ((uintptr_t)metrics_out & 7) ||
-        ((uintptr_t)sizes_out & 7))
-        return fail(RAE_E_INVALID, "table / gold_sizes / metrics_out / sizes_out must be 8-byte aligned");
+    if (const int rc = aligned({table, gold_sizes, metrics_out, sizes_out}, 7,
+                               "table / gold_sizes / metrics_out / sizes_out must be 8-byte aligned"))
+        return rc;
     hipLaunchKernelGGL(k_b3, dim3(1), dim3(RAE_B3_BT), 0, (hipStream_t)stream,
                        (const long long*)table, (const long long*)gold_sizes,
                        (long long)n_assessable, (int)relations, (int)n_gold, metrics_out,
@@ -2211,21 +2246,19 @@ extern "C" int rae_b3_metrics(const int64_t* table, const int64_t* gold_sizes, i
 extern "C" int rae_row_keys(const int32_t* indptr, const int32_t* indices, const float* values,
                             const int32_t* key_of_feature, int64_t n_features, int64_t row0,
                             int64_t nrows, int32_t* keys_out, rae_stream_t stream) {
-    if (!indptr) return fail(RAE_E_INVALID, "indptr is NULL");
-    if (!indices) return fail(RAE_E_INVALID, "indices is NULL");
-    if (!key_of_feature) return fail(RAE_E_INVALID, "key_of_feature is NULL");
-    if (!keys_out) return fail(RAE_E_INVALID, "keys_out is NULL");
-    if (n_features < 0 || n_features >= (1ll << 31))
-        return fail(RAE_E_INVALID, "n_features must be in [0, 2^31)");
+    if (const int rc = not_null({{indptr, "indptr"}, {indices, "indices"},
+                                 {key_of_feature, "key_of_feature"}, {keys_out, "keys_out"}}))
+        return rc;
+    if (const int rc = count_range("n_features", n_features, 0)) return rc;
     if (row0 < 0) return fail(RAE_E_INVALID, "row0 must be >= 0");
-    if (nrows < 0 || nrows >= (1ll << 31)) return fail(RAE_E_INVALID, "nrows must be in [0, 2^31)");
-    if (((uintptr_t)indptr & 3) || ((uintptr_t)indices & 3) || ((uintptr_t)values & 3) ||
-        ((uintptr_t)key_of_feature & 3) || ((uintptr_t)keys_out & 3))
-        return fail(RAE_E_INVALID, "pointers must be 4-byte aligned");
+    if (const int rc = count_range("nrows", nrows, 0)) return rc;
+    if (const int rc = aligned({indptr, indices, values, key_of_feature, keys_out}, 3,
+                               "pointers must be 4-byte aligned"))
+        return rc;
     if (nrows == 0) return RAE_OK;
-    const int64_t per = 4 * (RAE_RK_BT / 64);             // rows per workgroup and round
+    const int64_t per = 4 * (RAE_RWK_BT / 64);            // rows per workgroup and round
     const int64_t grid = std::min<int64_t>((nrows + per - 1) / per, 65536);
-    hipLaunchKernelGGL(k_row_keys, dim3((unsigned)grid), dim3(RAE_RK_BT), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(k_row_keys, dim3((unsigned)grid), dim3(RAE_RWK_BT), 0, (hipStream_t)stream,
                        indptr, indices, values, key_of_feature, (long long)n_features,
                        (long long)row0, (long long)nrows, keys_out);
     HIPCHK(hipGetLastError());
@@ -2235,36 +2268,21 @@ extern "C" int rae_row_keys(const int32_t* indptr, const int32_t* indices, const
 extern "C" int rae_cluster_key_count(const int64_t* labels, const int32_t* keys, int64_t nrows,
                                      int32_t relations, int32_t n_keys, int32_t accumulate,
                                      int32_t* counts, rae_stream_t stream) {
-    if (!labels) return fail(RAE_E_INVALID, "labels is NULL");
-    if (!keys) return fail(RAE_E_INVALID, "keys is NULL");
-    if (!counts) return fail(RAE_E_INVALID, "counts is NULL");
-    if (relations < 1 || relations > 512)
-        return fail(RAE_E_INVALID, "relations must be in [1, 512]");
-    if (n_keys < 1 || n_keys > (1 << 22)) return fail(RAE_E_INVALID, "n_keys must be in [1, 2^22]");
+    if (const int rc = not_null({{labels, "labels"}, {keys, "keys"}, {counts, "counts"}})) return rc;
+    if (const int rc = relations_range(relations)) return rc;
+    if (const int rc = key_count(n_keys)) return rc;
     const int64_t cells = (int64_t)relations * n_keys;
     if (cells > (1ll << 27)) return fail(RAE_E_INVALID, "relations * n_keys must be <= 2^27");
-    if (nrows < 0 || nrows >= (1ll << 31)) return fail(RAE_E_INVALID, "nrows must be in [0, 2^31)");
-    if (((uintptr_t)labels & 7) || ((uintptr_t)keys & 3) || ((uintptr_t)counts & 3))
-        return fail(RAE_E_INVALID, "labels / keys / counts must be aligned to their element size");
+    if (const int rc = count_range("nrows", nrows, 0)) return rc;
+    const char* al = "labels / keys / counts must be aligned to their element size";
+    if (const int rc = aligned({labels}, 7, al)) return rc;
+    if (const int rc = aligned({keys, counts}, 3, al)) return rc;
     hipStream_t st = (hipStream_t)stream;
     unsigned* ct = (unsigned*)counts;
-    if (!accumulate) {
-        const int64_t zg = std::min<int64_t>((cells + 255) / 256, 4096);
-        hipLaunchKernelGGL(k_ck_zero, dim3((unsigned)zg), dim3(256), 0, st, ct, (long long)cells);
-        HIPCHK(hipGetLastError());
-    }
+    if (const int rc = zero_unless(accumulate != 0, ct, cells, 4096, st)) return rc;
     if (nrows == 0) return RAE_OK;
-    // rows before the first index at which both pointers are 16-byte aligned (GV); with none,
-    // the labels alone are aligned and the keys are read as dwords
-    int head = -1;
-    for (int h = 0; h < 4; ++h)
-        if ((((uintptr_t)(labels + h)) & 15) == 0 && (((uintptr_t)(keys + h)) & 15) == 0) {
-            head = h;
-            break;
-        }
-    const bool gv = head >= 0;
-    if (!gv) head = ((uintptr_t)labels & 15) ? 1 : 0;
-    if (head > nrows) head = (int)nrows;
+    bool gv;
+    const int head = pair_head(labels, keys, nrows, &gv);
     const int64_t nq = (nrows - head) >> 2;
     const int64_t per = (int64_t)RAE_CK_BT * RAE_CK_QPT;
     const int64_t grid = std::max<int64_t>(1, std::min<int64_t>((nq + per - 1) / per, RAE_CK_GRID));
@@ -2280,16 +2298,16 @@ extern "C" int rae_cluster_key_count(const int64_t* labels, const int32_t* keys,
 extern "C" int rae_cluster_topk(const int32_t* counts, int32_t relations, int32_t n_keys,
                                 int64_t ld, int32_t top, int32_t* keys_out, int32_t* counts_out,
                                 rae_stream_t stream) {
-    if (!counts) return fail(RAE_E_INVALID, "counts is NULL");
-    if (!keys_out) return fail(RAE_E_INVALID, "keys_out is NULL");
-    if (!counts_out) return fail(RAE_E_INVALID, "counts_out is NULL");
-    if (relations < 1 || relations > 512)
-        return fail(RAE_E_INVALID, "relations must be in [1, 512]");
-    if (n_keys < 1 || n_keys > (1 << 22)) return fail(RAE_E_INVALID, "n_keys must be in [1, 2^22]");
+    if (const int rc = not_null({{counts, "counts"}, {keys_out, "keys_out"},
+                                 {counts_out, "counts_out"}}))
+        return rc;
+    if (const int rc = relations_range(relations)) return rc;
+    if (const int rc = key_count(n_keys)) return rc;
     if (ld < n_keys) return fail(RAE_E_INVALID, "ld must be >= n_keys");
     if (top < 1 || top > RAE_TK_MAXTOP) return fail(RAE_E_INVALID, "top must be in [1, 32]");
-    if (((uintptr_t)counts & 3) || ((uintptr_t)keys_out & 3) || ((uintptr_t)counts_out & 3))
-        return fail(RAE_E_INVALID, "counts / keys_out / counts_out must be 4-byte aligned");
+    if (const int rc = aligned({counts, keys_out, counts_out}, 3,
+                               "counts / keys_out / counts_out must be 4-byte aligned"))
+        return rc;
     hipLaunchKernelGGL(k_ctopk, dim3((unsigned)relations), dim3(RAE_TK_BT), 0, (hipStream_t)stream,
                        (const int*)counts, (int)n_keys, (long long)ld, (int)top, keys_out,
                        counts_out);
@@ -2302,39 +2320,28 @@ extern "C" int rae_feature_support(const int32_t* indptr, const int32_t* indices
                                    const float* values, int64_t n_features, int64_t row0,
                                    int64_t nrows, int32_t accumulate, int32_t* support,
                                    rae_stream_t stream) {
-    if (!indptr) return fail(RAE_E_INVALID, "indptr is NULL");
-    if (!indices) return fail(RAE_E_INVALID, "indices is NULL");
-    if (!support) return fail(RAE_E_INVALID, "support is NULL");
-    if (n_features < 0 || n_features >= (1ll << 31))
-        return fail(RAE_E_INVALID, "n_features must be in [0, 2^31)");
+    if (const int rc = not_null({{indptr, "indptr"}, {indices, "indices"}, {support, "support"}}))
+        return rc;
+    if (const int rc = count_range("n_features", n_features, 0)) return rc;
     if (row0 < 0) return fail(RAE_E_INVALID, "row0 must be >= 0");
-    if (nrows < 0 || nrows >= (1ll << 31)) return fail(RAE_E_INVALID, "nrows must be in [0, 2^31)");
-    if (((uintptr_t)indptr & 3) || ((uintptr_t)indices & 3) || ((uintptr_t)values & 3) ||
-        ((uintptr_t)support & 3))
-        return fail(RAE_E_INVALID, "indptr / indices / values / support must be 4-byte aligned");
+    if (const int rc = count_range("nrows", nrows, 0)) return rc;
+    if (const int rc = aligned({indptr, indices, values, support}, 3,
+                               "indptr / indices / values / support must be 4-byte aligned"))
+        return rc;
     hipStream_t st = (hipStream_t)stream;
     unsigned* sp = (unsigned*)support;
     if (n_features == 0) return RAE_OK;       // no cell to zero or count
-    if (!accumulate) {
-        const int64_t zg = std::min<int64_t>((n_features + 255) / 256, 4096);
-        hipLaunchKernelGGL(k_ck_zero, dim3((unsigned)zg), dim3(256), 0, st, sp, (long long)n_features);
-        HIPCHK(hipGetLastError());
-    }
+    if (const int rc = zero_unless(accumulate != 0, sp, n_features, 4096, st)) return rc;
     if (nrows == 0) return RAE_OK;
     const int64_t grid = std::max<int64_t>(1, std::min<int64_t>(ceil_div(nrows, (int64_t)RAE_FS_ROWS),
                                                                 RAE_FS_GRID));
     // values by 16-byte loads when they are aligned where the indices are
     const int vm = !values ? 0 : ((((uintptr_t)values ^ (uintptr_t)indices) & 15) == 0 ? 1 : 2);
-    const dim3 g((unsigned)grid), b(RAE_FS_BT);
-    if (vm == 0)
-        hipLaunchKernelGGL(k_fsupport<0>, g, b, 0, st, indptr, indices, values,
-                           (long long)n_features, (long long)row0, (long long)nrows, sp);
-    else if (vm == 1)
-        hipLaunchKernelGGL(k_fsupport<1>, g, b, 0, st, indptr, indices, values,
-                           (long long)n_features, (long long)row0, (long long)nrows, sp);
-    else
-        hipLaunchKernelGGL(k_fsupport<2>, g, b, 0, st, indptr, indices, values,
-                           (long long)n_features, (long long)row0, (long long)nrows, sp);
+    with_vm(vm, [&](auto Vm) {
+        hipLaunchKernelGGL(k_fsupport<RAE_CV(Vm)>, dim3((unsigned)grid), dim3(RAE_FS_BT), 0, st,
+                           indptr, indices, values, (long long)n_features, (long long)row0,
+                           (long long)nrows, sp);
+    });
     HIPCHK(hipGetLastError());
     return RAE_OK;
 }
@@ -2344,10 +2351,8 @@ struct FtopkLayout { size_t o_keys, o_mean, total; int strips; };
 // shapes of rae_feature_topk and its workspace layout (host only)
 int ftopk_layout(const rae_ftopk_args* a, FtopkLayout& L) {
     if (!a) return fail(RAE_E_INVALID, "null argument");
-    if (a->relations < 1 || a->relations > 512)
-        return fail(RAE_E_INVALID, "relations must be in [1, 512]");
-    if (a->n_features < 0 || a->n_features >= (1ll << 31))
-        return fail(RAE_E_INVALID, "n_features must be in [0, 2^31)");
+    if (const int rc = relations_range(a->relations)) return rc;
+    if (const int rc = count_range("n_features", a->n_features, 0)) return rc;
     if (a->ldw < a->relations) return fail(RAE_E_INVALID, "ldw is smaller than relations");
     if (const int rc = topk_top(a->top)) return rc;
     if (a->centre != 0 && a->centre != 1) return fail(RAE_E_INVALID, "centre must be 0 or 1");
@@ -2370,9 +2375,9 @@ extern "C" int rae_feature_topk(const rae_ftopk_args* a, rae_stream_t stream) {
     if (const int rc = ftopk_layout(a, L)) return rc;
     if (a->n_features > 0 && !a->W) return fail(RAE_E_INVALID, "W is NULL");
     if (!a->feats_out) return fail(RAE_E_INVALID, "feats_out is NULL");
-    if (((uintptr_t)a->W & 3) || ((uintptr_t)a->support & 3) || ((uintptr_t)a->feats_out & 3) ||
-        ((uintptr_t)a->scores_out & 3))
-        return fail(RAE_E_INVALID, "W / support / feats_out / scores_out must be 4-byte aligned");
+    if (const int rc = aligned({a->W, a->support, a->feats_out, a->scores_out}, 3,
+                               "W / support / feats_out / scores_out must be 4-byte aligned"))
+        return rc;
     if (const int rc = check_workspace(a->workspace, a->workspace_bytes, L.total,
                                        "rae_feature_topk_workspace_bytes"))
         return rc;

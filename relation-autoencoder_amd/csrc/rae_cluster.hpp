@@ -68,6 +68,58 @@ __device__ __forceinline__ void cc_add(int cell, unsigned* cnt, unsigned long lo
     }
 }
 
+// The stream of (int64 label, int32 second) row pairs that k_ccount and rae_profile.hpp's k_ckcount
+// share: row(label, second) once per row of [0, nrows), for a grid of BT-thread workgroups.  Four
+// consecutive rows per lane and round over the 16-byte aligned middle (two quads in flight), the
+// up to 3 + 3 rows of the unaligned head [0, head) and the tail from workgroup 0.  GV: `second`
+// is aligned where the labels are; otherwise its quads are read as dwords.
+template <bool GV, int BT, class F>
+__device__ __forceinline__ void row_pair_stream(const long long* labels, const int* second,
+                                                long long nrows, int head, F&& row) {
+    const long long nq = (nrows - head) >> 2;             // quads of the aligned middle
+    const long long tail0 = head + 4 * nq;
+    const long long stride = (long long)gridDim.x * BT;
+    const rae_v2l* lv = reinterpret_cast<const rae_v2l*>(labels + head);
+    const int* sm = second + head;
+    for (long long q = (long long)blockIdx.x * BT + threadIdx.x; q < nq; q += 2 * stride) {
+        const long long q1 = q + stride;
+        const bool two = q1 < nq;
+        const long long qb = two ? q1 : q;                // in range either way
+        const rae_v2l a0 = __builtin_nontemporal_load(lv + 2 * q);
+        const rae_v2l a1 = __builtin_nontemporal_load(lv + 2 * q + 1);
+        const rae_v2l b0 = __builtin_nontemporal_load(lv + 2 * qb);
+        const rae_v2l b1 = __builtin_nontemporal_load(lv + 2 * qb + 1);
+        rae_v4i sa, sb;
+        if (GV) {
+            sa = __builtin_nontemporal_load(reinterpret_cast<const rae_v4i*>(sm) + q);
+            sb = __builtin_nontemporal_load(reinterpret_cast<const rae_v4i*>(sm) + qb);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                sa[k] = __builtin_nontemporal_load(sm + 4 * q + k);
+                sb[k] = __builtin_nontemporal_load(sm + 4 * qb + k);
+            }
+        }
+        row(a0.x, sa.x);
+        row(a0.y, sa.y);
+        row(a1.x, sa.z);
+        row(a1.y, sa.w);
+        if (two) {
+            row(b0.x, sb.x);
+            row(b0.y, sb.y);
+            row(b1.x, sb.z);
+            row(b1.y, sb.w);
+        }
+    }
+    // the unaligned head [0, head) and the tail [tail0, nrows): at most 3 + 3 rows
+    if (blockIdx.x == 0 && threadIdx.x < 8) {
+        const int t = threadIdx.x;
+        const long long i = t < 4 ? (long long)t : tail0 + (t - 4);
+        const bool in = t < 4 ? (t < head && i < nrows) : i < nrows;
+        if (in) row(labels[i], second[i]);
+    }
+}
+
 template <bool LDS, bool GV>
 __global__ __launch_bounds__(RAE_CC_BT) void k_ccount(const long long* __restrict__ labels,
                                                       const int* __restrict__ gold,
@@ -79,48 +131,9 @@ __global__ __launch_bounds__(RAE_CC_BT) void k_ccount(const long long* __restric
         for (int i = threadIdx.x; i < cells; i += RAE_CC_BT) cc_cnt[i] = 0u;
         __syncthreads();
     }
-    const long long nq = (nrows - head) >> 2;             // quads of the aligned middle
-    const long long tail0 = head + 4 * nq;
-    const long long stride = (long long)gridDim.x * RAE_CC_BT;
-    const rae_v2l* lv = reinterpret_cast<const rae_v2l*>(labels + head);
-    const int* gm = gold + head;
-    for (long long q = (long long)blockIdx.x * RAE_CC_BT + threadIdx.x; q < nq; q += 2 * stride) {
-        const long long q1 = q + stride;
-        const bool two = q1 < nq;
-        const long long qb = two ? q1 : q;                // in range either way
-        const rae_v2l a0 = __builtin_nontemporal_load(lv + 2 * q);
-        const rae_v2l a1 = __builtin_nontemporal_load(lv + 2 * q + 1);
-        const rae_v2l b0 = __builtin_nontemporal_load(lv + 2 * qb);
-        const rae_v2l b1 = __builtin_nontemporal_load(lv + 2 * qb + 1);
-        rae_v4i ga, gb;
-        if (GV) {
-            ga = __builtin_nontemporal_load(reinterpret_cast<const rae_v4i*>(gm) + q);
-            gb = __builtin_nontemporal_load(reinterpret_cast<const rae_v4i*>(gm) + qb);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                ga[k] = __builtin_nontemporal_load(gm + 4 * q + k);
-                gb[k] = __builtin_nontemporal_load(gm + 4 * qb + k);
-            }
-        }
-        cc_add<LDS>(cc_cell(a0.x, ga.x, m, ng), cc_cnt, table);
-        cc_add<LDS>(cc_cell(a0.y, ga.y, m, ng), cc_cnt, table);
-        cc_add<LDS>(cc_cell(a1.x, ga.z, m, ng), cc_cnt, table);
-        cc_add<LDS>(cc_cell(a1.y, ga.w, m, ng), cc_cnt, table);
-        if (two) {
-            cc_add<LDS>(cc_cell(b0.x, gb.x, m, ng), cc_cnt, table);
-            cc_add<LDS>(cc_cell(b0.y, gb.y, m, ng), cc_cnt, table);
-            cc_add<LDS>(cc_cell(b1.x, gb.z, m, ng), cc_cnt, table);
-            cc_add<LDS>(cc_cell(b1.y, gb.w, m, ng), cc_cnt, table);
-        }
-    }
-    // the unaligned head [0, head) and the tail [tail0, nrows): at most 3 + 3 rows
-    if (blockIdx.x == 0 && threadIdx.x < 8) {
-        const int t = threadIdx.x;
-        const long long i = t < 4 ? (long long)t : tail0 + (t - 4);
-        const bool in = t < 4 ? (t < head && i < nrows) : i < nrows;
-        if (in) cc_add<LDS>(cc_cell(labels[i], gold[i], m, ng), cc_cnt, table);
-    }
+    row_pair_stream<GV, RAE_CC_BT>(labels, gold, nrows, head, [&](long long c, int g) {
+        cc_add<LDS>(cc_cell(c, g, m, ng), cc_cnt, table);
+    });
     if (LDS) {
         __syncthreads();
         for (int i = threadIdx.x; i < cells; i += RAE_CC_BT) {
@@ -130,11 +143,11 @@ __global__ __launch_bounds__(RAE_CC_BT) void k_ccount(const long long* __restric
     }
 }
 
-__global__ __launch_bounds__(256) void k_cc_zero(unsigned long long* __restrict__ table,
-                                                 long long cells) {
+// p[0, n) = 0: the tables of the counting entries (T = their cell type)
+template <class T>
+__global__ __launch_bounds__(256) void k_zero(T* __restrict__ p, long long n) {
     const long long stride = (long long)gridDim.x * 256;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < cells; i += stride)
-        table[i] = 0ull;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) p[i] = T(0);
 }
 
 // rae/evaluation.py compute_metrics from the table; out = { f1, precision, recall,

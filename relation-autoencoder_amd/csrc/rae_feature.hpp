@@ -35,8 +35,8 @@
 // load) and an ineligible row is not read.  The scores (NaN = no candidate) go to an LDS tile of
 // odd pitch, and the next tile's loads are issued before the tile is consumed.  Selecting, a WAVE
 // owns RAE_FT_CPW = 8 columns: lane j reads row j of a column from the tile (conflict-free), packs
-// orderable(score) << 32 | ~feature (rae_topk.hpp topk_key) and offers it to the column's list,
-// held sorted across the lanes of the wave (rae_profile.hpp tk_offer: lane j the j-th best, the
+// orderable(score) << 32 | ~feature (rae_key.hpp topk_key) and offers it to the column's list,
+// held sorted across the lanes of the wave (rae_key.hpp tk_offer: lane j the j-th best, the
 // top-th as the admission threshold): a ballot per 64 rows and column, and after warm-up almost no
 // admission (about top ln(rows / top) per list and strip).  The first form of this kernel kept a
 // list per THREAD in LDS; there a wave pays for an admission whenever any of its 64 columns
@@ -59,8 +59,8 @@
 // of its row of W (centred) or its cell (raw), so a relation's output row does not depend on the
 // other relations' values either (centred: beyond the row sums they enter).
 #pragma once
+#include "rae_key.hpp"
 #include "rae_profile.hpp"
-#include "rae_topk.hpp"
 
 #define RAE_FS_BT 256                 // k_fsupport: threads per workgroup
 #define RAE_FS_GRID 2048              // workgroups at most
@@ -101,18 +101,7 @@ __global__ __launch_bounds__(RAE_FS_BT) void k_fsupport(const int32_t* __restric
                                                         long long n_features, long long row0,
                                                         long long nrows,
                                                         unsigned* __restrict__ support) {
-#if RAE_CK_AGG
-    __shared__ int tag[1 << RAE_CK_SLOT_BITS];
-    __shared__ unsigned cnt[1 << RAE_CK_SLOT_BITS];
-    for (int i = threadIdx.x; i < (1 << RAE_CK_SLOT_BITS); i += RAE_FS_BT) {
-        tag[i] = -1;
-        cnt[i] = 0u;
-    }
-    __syncthreads();
-#else
-    int* tag = nullptr;
-    unsigned* cnt = nullptr;
-#endif
+    const CkSlots s = ck_slots_init<RAE_FS_BT>();
     const long long p0 = indptr[row0], p1 = indptr[row0 + nrows];
     const long long n = p1 > p0 ? p1 - p0 : 0;
     // entries before the first 16-byte boundary of indices
@@ -134,7 +123,7 @@ __global__ __launch_bounds__(RAE_FS_BT) void k_fsupport(const int32_t* __restric
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const bool in = f[k] >= 0 && f[k] < n_features && v[k] != 0.f;
-            ck_add(in ? f[k] : -1, tag, cnt, support);
+            ck_add(in ? f[k] : -1, s.tag, s.cnt, support);
         }
     }
     // the unaligned head [p0, mid) and the tail [tail0, p1): at most 3 + 3 entries
@@ -145,16 +134,10 @@ __global__ __launch_bounds__(RAE_FS_BT) void k_fsupport(const int32_t* __restric
         if (in) {
             const int f = indices[i];
             const bool ok = f >= 0 && f < n_features && (VM == 0 || values[i] != 0.f);
-            ck_add(ok ? f : -1, tag, cnt, support);
+            ck_add(ok ? f : -1, s.tag, s.cnt, support);
         }
     }
-#if RAE_CK_AGG
-    __syncthreads();
-    for (int i = threadIdx.x; i < (1 << RAE_CK_SLOT_BITS); i += RAE_FS_BT) {
-        const unsigned c = cnt[i];
-        if (c) atomicAdd(&support[tag[i]], c);
-    }
-#endif
+    ck_slots_flush<RAE_FS_BT>(s, support);
 }
 
 __global__ __launch_bounds__(RAE_FR_BT) void k_frowstat(const float* __restrict__ W, long long d,
@@ -213,7 +196,7 @@ __device__ __forceinline__ void ftopk_select(const FtopkArgs& a, float* T) {
     const long long s0 = (long long)blockIdx.y * a.strip_rows;
     const long long s1 = s0 + a.strip_rows < a.d ? s0 + a.strip_rows : a.d;
     const float* Wc = a.W + col;
-    unsigned long long list[RAE_FT_CPW], thr[RAE_FT_CPW];    // lane j: the column's j-th best
+    rae_key64 list[RAE_FT_CPW], thr[RAE_FT_CPW];       // lane j: the column's j-th best
 #pragma unroll
     for (int c = 0; c < RAE_FT_CPW; ++c) list[c] = thr[c] = 0ull;
     float x[RAE_FT_U];
@@ -273,7 +256,7 @@ __device__ __forceinline__ void ftopk_finish(const rae_key64* __restrict__ keys,
     const int col = blockIdx.x * RAE_FT_FQ + w;
     if (col >= m) return;                                 // the whole wave; no barrier below
     const int l31 = lane & 31, h = lane >> 5;
-    unsigned long long list = 0ull, thr = 0ull;
+    rae_key64 list = 0ull, thr = 0ull;
     rae_key64 cur[RAE_FT_FU], nxt[RAE_FT_FU];
     auto load = [&](int s, rae_key64 (&v)[RAE_FT_FU]) {
 #pragma unroll
@@ -290,11 +273,7 @@ __device__ __forceinline__ void ftopk_finish(const rae_key64* __restrict__ keys,
 #pragma unroll
         for (int u = 0; u < RAE_FT_FU; ++u) cur[u] = nxt[u];
     }
-    if (lane < top) {
-        const bool has = list != 0ull;
-        feats[(long long)col * top + lane] = has ? (int32_t)~(unsigned)list : -1;
-        if (scores) scores[(long long)col * top + lane] = has ? topk_score(list) : -INFINITY;
-    }
+    if (lane < top) key_unpack_store(list, feats, scores, (long long)col * top + lane);
 }
 
 template <bool CENTRE>

@@ -11,10 +11,10 @@
 // taken from the wave's ballot.  key_of_feature (4 d bytes) stays in cache.
 //
 // k_ckcount: counts[c * n_keys + k] += |{ i : labels[i] == c, keys[i] == k }|, rows with a label
-// or key out of range skipped.  k_ccount's stream (12 bytes per row, four consecutive rows per
-// lane and round from two 16-byte label loads and one 16-byte key load over the aligned middle,
-// the up to 3 + 3 rows around it one by one) and 32-bit atomics into the table: tens of thousands
-// of columns have no LDS form of the whole table.  Triggers are Zipf-distributed and early
+// or key out of range skipped.  k_ccount's stream (rae_cluster.hpp row_pair_stream: 12 bytes per
+// row, four consecutive rows per lane and round over the aligned middle, the up to 3 + 3 rows
+// around it one by one) and 32-bit atomics into the table: tens of thousands of columns have no
+// LDS form of the whole table.  Triggers are Zipf-distributed and early
 // clusters are few, so many rows hit a few cells, and the atomics of all CUs on one cache line
 // are served one after another (~3 x 10^2 per us measured).  Two measures against that:
 //  - cc_add's rule: a wave instruction whose active lanes all hold one cell adds their number
@@ -31,18 +31,18 @@
 // the atomics they save)
 //
 // k_ctopk: one workgroup of 16 waves per table row, one pass over the row.  A cell is the
-// packed 64-bit value count << 32 | ~key, so unsigned order = count descending, then key
-// ascending (total: the output is unique), 0 = no cell.  Every wave keeps the 64 best cells it
-// has seen sorted across its lanes (lane j the j-th best) and the top-th of them as the
-// admission threshold: a round loads 8 x 64 cells, ballots the ones above the threshold (after
-// warm-up almost none) and inserts each -- its rank is the popcount of the ballot of the larger
-// list entries, the entries behind it move up one lane.  The waves' lists meet in LDS and wave
-// 0 takes them through the same insertion.
+// packed 64-bit value count << 32 | ~key (rae_key.hpp count_key), so unsigned order = count
+// descending, then key ascending (total: the output is unique), 0 = no cell.  Every wave keeps
+// the 64 best cells it has seen sorted across its lanes and the top-th of them as the admission
+// threshold (rae_key.hpp tk_offer): a round loads 8 x 64 cells, ballots the ones above the
+// threshold (after warm-up almost none) and inserts each -- its rank is the popcount of the
+// ballot of the larger list entries, the entries behind it move up one lane.  The waves' lists
+// meet in LDS and wave 0 takes them through the same insertion.
 #pragma once
 #include "rae_cluster.hpp"
-#include "rae_common.hpp"
+#include "rae_key.hpp"
 
-#define RAE_RK_BT 256                 // k_row_keys: 4 waves x 4 rows per round
+#define RAE_RWK_BT 256                // k_row_keys: 4 waves x 4 rows per round
 #define RAE_CK_BT 256                 // threads per workgroup of k_ckcount
 #define RAE_CK_QPT 4                  // row quads per thread the grid is sized for
 #define RAE_CK_GRID 2048              // workgroups at most
@@ -56,17 +56,17 @@
 
 namespace rae {
 
-__global__ __launch_bounds__(RAE_RK_BT) void k_row_keys(const int32_t* __restrict__ indptr,
-                                                        const int32_t* __restrict__ indices,
-                                                        const float* __restrict__ values,
-                                                        const int32_t* __restrict__ kof,
-                                                        long long n_features, long long row0,
-                                                        long long nrows,
-                                                        int32_t* __restrict__ keys) {
+__global__ __launch_bounds__(RAE_RWK_BT) void k_row_keys(const int32_t* __restrict__ indptr,
+                                                         const int32_t* __restrict__ indices,
+                                                         const float* __restrict__ values,
+                                                         const int32_t* __restrict__ kof,
+                                                         long long n_features, long long row0,
+                                                         long long nrows,
+                                                         int32_t* __restrict__ keys) {
     const int lane = threadIdx.x & 63, sub = lane & 15, grp = lane >> 4;
-    const long long nw = (long long)gridDim.x * (RAE_RK_BT / 64);
+    const long long nw = (long long)gridDim.x * (RAE_RWK_BT / 64);
     const long long rounds = (nrows + 4 * nw - 1) / (4 * nw);      // the same for every wave
-    long long w = (long long)blockIdx.x * (RAE_RK_BT / 64) + (threadIdx.x >> 6);
+    long long w = (long long)blockIdx.x * (RAE_RWK_BT / 64) + (threadIdx.x >> 6);
     for (long long it = 0; it < rounds; ++it, w += nw) {
         const long long e = 4 * w + grp;
         const bool valid = e < nrows;
@@ -125,112 +125,59 @@ __device__ __forceinline__ void ck_add(int cell, int* __restrict__ tag, unsigned
     atomicAdd(&counts[cell], n);
 }
 
+// the workgroup's LDS slots of ck_add, (tag, counter) each, for a workgroup of BT threads: cleared
+// by ck_slots_init, the non-zero counters added to `counts` by ck_slots_flush.  RAE_CK_AGG = 0:
+// there are none
+struct CkSlots {
+    int* tag;
+    unsigned* cnt;
+};
+template <int BT>
+__device__ __forceinline__ CkSlots ck_slots_init() {
+#if RAE_CK_AGG
+    __shared__ int tag[1 << RAE_CK_SLOT_BITS];
+    __shared__ unsigned cnt[1 << RAE_CK_SLOT_BITS];
+    for (int i = threadIdx.x; i < (1 << RAE_CK_SLOT_BITS); i += BT) {
+        tag[i] = -1;
+        cnt[i] = 0u;
+    }
+    __syncthreads();
+    return {tag, cnt};
+#else
+    return {nullptr, nullptr};
+#endif
+}
+template <int BT>
+__device__ __forceinline__ void ck_slots_flush(const CkSlots& s, unsigned* counts) {
+#if RAE_CK_AGG
+    __syncthreads();
+    for (int i = threadIdx.x; i < (1 << RAE_CK_SLOT_BITS); i += BT) {
+        const unsigned v = s.cnt[i];
+        if (v) atomicAdd(&counts[s.tag[i]], v);
+    }
+#endif
+}
+
 template <bool GV>
 __global__ __launch_bounds__(RAE_CK_BT) void k_ckcount(const long long* __restrict__ labels,
                                                        const int* __restrict__ keys,
                                                        long long nrows, int head, int m, int nk,
                                                        unsigned* __restrict__ counts) {
-#if RAE_CK_AGG
-    __shared__ int tag[1 << RAE_CK_SLOT_BITS];
-    __shared__ unsigned cnt[1 << RAE_CK_SLOT_BITS];
-    for (int i = threadIdx.x; i < (1 << RAE_CK_SLOT_BITS); i += RAE_CK_BT) {
-        tag[i] = -1;
-        cnt[i] = 0u;
-    }
-    __syncthreads();
-#else
-    int* tag = nullptr;
-    unsigned* cnt = nullptr;
-#endif
-    const long long nq = (nrows - head) >> 2;             // quads of the aligned middle
-    const long long tail0 = head + 4 * nq;
-    const long long stride = (long long)gridDim.x * RAE_CK_BT;
-    const rae_v2l* lv = reinterpret_cast<const rae_v2l*>(labels + head);
-    const int* km = keys + head;
-    for (long long q = (long long)blockIdx.x * RAE_CK_BT + threadIdx.x; q < nq; q += 2 * stride) {
-        const long long q1 = q + stride;
-        const bool two = q1 < nq;
-        const long long qb = two ? q1 : q;                // in range either way
-        const rae_v2l a0 = __builtin_nontemporal_load(lv + 2 * q);
-        const rae_v2l a1 = __builtin_nontemporal_load(lv + 2 * q + 1);
-        const rae_v2l b0 = __builtin_nontemporal_load(lv + 2 * qb);
-        const rae_v2l b1 = __builtin_nontemporal_load(lv + 2 * qb + 1);
-        rae_v4i ka, kb;
-        if (GV) {
-            ka = __builtin_nontemporal_load(reinterpret_cast<const rae_v4i*>(km) + q);
-            kb = __builtin_nontemporal_load(reinterpret_cast<const rae_v4i*>(km) + qb);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                ka[k] = __builtin_nontemporal_load(km + 4 * q + k);
-                kb[k] = __builtin_nontemporal_load(km + 4 * qb + k);
-            }
-        }
-        ck_add(ck_cell(a0.x, ka.x, m, nk), tag, cnt, counts);
-        ck_add(ck_cell(a0.y, ka.y, m, nk), tag, cnt, counts);
-        ck_add(ck_cell(a1.x, ka.z, m, nk), tag, cnt, counts);
-        ck_add(ck_cell(a1.y, ka.w, m, nk), tag, cnt, counts);
-        if (two) {
-            ck_add(ck_cell(b0.x, kb.x, m, nk), tag, cnt, counts);
-            ck_add(ck_cell(b0.y, kb.y, m, nk), tag, cnt, counts);
-            ck_add(ck_cell(b1.x, kb.z, m, nk), tag, cnt, counts);
-            ck_add(ck_cell(b1.y, kb.w, m, nk), tag, cnt, counts);
-        }
-    }
-    // the unaligned head [0, head) and the tail [tail0, nrows): at most 3 + 3 rows
-    if (blockIdx.x == 0 && threadIdx.x < 8) {
-        const int t = threadIdx.x;
-        const long long i = t < 4 ? (long long)t : tail0 + (t - 4);
-        const bool in = t < 4 ? (t < head && i < nrows) : i < nrows;
-        if (in) ck_add(ck_cell(labels[i], keys[i], m, nk), tag, cnt, counts);
-    }
-#if RAE_CK_AGG
-    __syncthreads();
-    for (int i = threadIdx.x; i < (1 << RAE_CK_SLOT_BITS); i += RAE_CK_BT) {
-        const unsigned v = cnt[i];
-        if (v) atomicAdd(&counts[tag[i]], v);
-    }
-#endif
-}
-
-__global__ __launch_bounds__(256) void k_ck_zero(unsigned* __restrict__ counts, long long cells) {
-    const long long stride = (long long)gridDim.x * 256;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < cells; i += stride)
-        counts[i] = 0u;
-}
-
-__device__ __forceinline__ unsigned long long tk_readlane(unsigned long long v, int l) {
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l);
-    return ((unsigned long long)hi << 32) | lo;
-}
-
-// offer one packed cell per lane (0 = none) to the wave's sorted list; every lane of the wave
-// calls it (the loop and its branch are wave-uniform)
-__device__ __forceinline__ void tk_offer(unsigned long long v, unsigned long long& list,
-                                         unsigned long long& thr, int top, int lane) {
-    unsigned long long cand = __ballot(v > thr);
-    while (cand) {
-        const int src = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(cand));
-        cand &= cand - 1;
-        const unsigned long long c = tk_readlane(v, src);
-        if (c > thr) {                                    // the threshold may have risen
-            const int pos = __builtin_popcountll(__ballot(list > c));     // cells ahead of c
-            const unsigned long long up = __shfl_up(list, 1, 64);
-            list = lane < pos ? list : (lane == pos ? c : up);
-            thr = tk_readlane(list, top - 1);
-        }
-    }
+    const CkSlots s = ck_slots_init<RAE_CK_BT>();
+    row_pair_stream<GV, RAE_CK_BT>(labels, keys, nrows, head, [&](long long c, int k) {
+        ck_add(ck_cell(c, k, m, nk), s.tag, s.cnt, counts);
+    });
+    ck_slots_flush<RAE_CK_BT>(s, counts);
 }
 
 __global__ __launch_bounds__(RAE_TK_BT) void k_ctopk(const int* __restrict__ counts, int nk,
                                                      long long ld, int top,
                                                      int* __restrict__ keys_out,
                                                      int* __restrict__ counts_out) {
-    __shared__ unsigned long long s_list[(RAE_TK_BT / 64 - 1) * RAE_TK_MAXTOP];
+    __shared__ rae_key64 s_list[(RAE_TK_BT / 64 - 1) * RAE_TK_MAXTOP];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int* row = counts + (long long)blockIdx.x * ld;
-    unsigned long long list = 0ull, thr = 0ull;
+    rae_key64 list = 0ull, thr = 0ull;
     constexpr int SPAN = RAE_TK_BT * RAE_TK_U;            // cells per round of the workgroup
     for (int base = w * 64 * RAE_TK_U; base < nk; base += SPAN) {
         int cnt[RAE_TK_U];
@@ -241,10 +188,7 @@ __global__ __launch_bounds__(RAE_TK_BT) void k_ctopk(const int* __restrict__ cou
         }
 #pragma unroll
         for (int u = 0; u < RAE_TK_U; ++u) {
-            const unsigned k = (unsigned)(base + 64 * u + lane);
-            const unsigned long long v =
-                cnt[u] > 0 ? ((unsigned long long)(unsigned)cnt[u] << 32) | (unsigned)~k : 0ull;
-            tk_offer(v, list, thr, top, lane);
+            tk_offer(count_key(cnt[u], (unsigned)(base + 64 * u + lane)), list, thr, top, lane);
         }
     }
     if (w > 0 && lane < RAE_TK_MAXTOP) s_list[(w - 1) * RAE_TK_MAXTOP + lane] = list;

@@ -5,11 +5,9 @@
 // acc + (c + Ab[e]), so a score has the bits rae_rank_queries compares.  The (nq x n) matrix is
 // never stored: a selection epilogue keeps the best `top` of every query in LDS.
 //
-// A candidate is the packed 64-bit key  orderable(score) << 32 | ~entity  (rae_profile.hpp's
-// k_ctopk packs count << 32 | ~key the same way): -0 is made +0, then the sign bit of a
-// non-negative score is set and a negative score is inverted, so unsigned 64-bit order is score
-// descending, then entity ascending -- a total order.  A NaN score is no candidate.  The smallest
-// real key is -inf's (0x007fffff << 32), so 0 means "no entry".
+// A candidate is the packed 64-bit key  orderable(score) << 32 | ~entity  (rae_key.hpp topk_key):
+// unsigned 64-bit order is score descending, then entity ascending -- a total order.  A NaN score
+// is no candidate, and 0 means "no entry".
 //
 // Kernels:
 //   k_topk         workgroup (query tile, strip) as k_rank.  Per query of the workgroup LDS holds
@@ -45,6 +43,7 @@
 // A score is a function of its Q row, its A row, r, add and Ab (rae_rank.hpp), so an output row
 // does not depend on nq, the query's slot or the other queries.
 #pragma once
+#include "rae_key.hpp"
 #include "rae_rank.hpp"
 
 namespace rae {
@@ -59,30 +58,10 @@ namespace rae {
     ((RAE_RK_TQ * (RAE_ETK_LDKEPT + RAE_ETK_LDPEND + 1)) * 8 +                                  \
      (RAE_RK_TQ * RAE_RK_LDK + RAE_RK_TE * RAE_RK_LDK + RAE_RK_TE) * 4 + RAE_RK_TQ * 4)
 
-typedef unsigned long long rae_key64;
-
 struct TopkOut {
     rae_key64* keys;              // (strips, RAE_ETK_QCHUNK, top)
     int top;
 };
-
-__device__ __forceinline__ rae_key64 topk_key(float g, unsigned e) {
-    g = g == 0.f ? 0.f : g;                                   // -0 -> +0
-    const unsigned b = __float_as_uint(g);
-    const unsigned ord = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-    return ((rae_key64)ord << 32) | (rae_key64)(~e);
-}
-__device__ __forceinline__ float topk_score(rae_key64 key) {
-    const unsigned ord = (unsigned)(key >> 32);
-    return __uint_as_float((ord & 0x80000000u) ? (ord ^ 0x80000000u) : ~ord);
-}
-
-// the key held by lane i (i wave-uniform)
-__device__ __forceinline__ rae_key64 topk_lane_key(rae_key64 v, int i) {
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, i);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), i);
-    return ((rae_key64)hi << 32) | (rae_key64)lo;
-}
 
 // acc[entity tile][query tile] = the products <Q[q], A[e]> of the 128 x 128 tile at (q0, e0).
 // This is rank_scores' K loop, statement for statement (rank_load / rank_store shared): factoring
@@ -284,11 +263,7 @@ __device__ __forceinline__ void topk_finish(const rae_key64* __restrict__ keys, 
         cur = L[l31];
         __builtin_amdgcn_wave_barrier();
     }
-    if (lane < top) {
-        const bool has = cur != 0ull;
-        ents[(int64_t)q * top + lane] = has ? (int32_t)~(unsigned)cur : -1;
-        if (scores) scores[(int64_t)q * top + lane] = has ? topk_score(cur) : -INFINITY;
-    }
+    if (lane < top) key_unpack_store(cur, ents, scores, (long long)q * top + lane);
 }
 
 }  // namespace rae

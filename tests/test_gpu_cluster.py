@@ -109,14 +109,16 @@ def test_table_is_exact(built_lib, cuda_dev, shape):
                 _count(lib, torch, lab_d[off:off + n], gold_d[off:off + n], m, ng, form, tb)
                 if not torch.equal(tb, want):
                     bad.append((n, off, form, int((tb != want).sum())))
-    # labels and gold offset differently: no head aligns both (gold ids read as dwords)
+    # labels and gold offset differently: no head aligns both (gold ids read as dwords), after a
+    # head of 1 (1/2) or of none (0/1); and a common head of 2 (0/2)
     n = 4097
-    want = torch.as_tensor(contingency_table(lab[1:1 + n], _gi(gold[2:2 + n], ng), m).reshape(-1),
-                           device=cuda_dev)
-    for form in forms:
-        _count(lib, torch, lab_d[1:1 + n], gold_d[2:2 + n], m, ng, form, tb)
-        if not torch.equal(tb, want):
-            bad.append((n, "1/2", form, int((tb != want).sum())))
+    for lo, go in ((1, 2), (0, 1), (0, 2)):
+        want = torch.as_tensor(contingency_table(lab[lo:lo + n], _gi(gold[go:go + n], ng), m)
+                               .reshape(-1), device=cuda_dev)
+        for form in forms:
+            _count(lib, torch, lab_d[lo:lo + n], gold_d[go:go + n], m, ng, form, tb)
+            if not torch.equal(tb, want):
+                bad.append((n, f"{lo}/{go}", form, int((tb != want).sum())))
     assert not bad, bad
 
 

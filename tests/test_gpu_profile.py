@@ -124,8 +124,9 @@ def test_row_keys(built_lib, cuda_dev):
 KEY_SHAPES = [(1, 1), (3, 5), (100, 481), (512, 4097), (7, 100003)]
 KINDS = ["uniform", "zipf", "one-cell", "one-cluster"]
 # (labels offset, keys offset) in elements: both 16-byte aligned; a head of 1; no common head
-# (the keys of the middle are read as dwords); a head of 2
-VIEWS = [(0, 0), (1, 3), (1, 2), (0, 2)]
+# (the keys of the middle are read as dwords); a head of 2; no common head with the labels
+# aligned (dwords again, no head at all); a head of 3
+VIEWS = [(0, 0), (1, 3), (1, 2), (0, 2), (0, 1), (1, 1)]
 
 
 def _key_count(lib, torch, lab, key, n, m, nk, acc, table):
