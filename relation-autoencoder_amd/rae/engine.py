@@ -75,6 +75,42 @@ def check_p2p_devices(identities, cross_device: bool):
             "use dp_xchg='collective', the default)")
 
 
+IndexSchedule = collections.namedtuple("IndexSchedule", "overlap window lookahead")
+
+
+def resolve_index_schedule(index_window: int, index_overlap: bool, pipelined: bool,
+                           nb: int | None = None) -> IndexSchedule:
+    """How run() walks a row-index ring of `index_window` batches (the plan's value,
+    rae_index_window: already clamped to the epoch): IndexSchedule(overlap, window, lookahead).
+
+    A window's steps read `window + lookahead` slots: their own batches and, pipelined
+    peer-to-peer form, the row lists of the batch after the last one (every step pushes the
+    NEXT batch's rows).  With overlap the side stream writes up to `window` further slots while
+    those steps run, and a build must never write a slot a queued step reads (prefetch_index),
+    so overlap needs  index_window >= 2 * window + lookahead  with window >= 1: a ring of 2
+    batches, of 3 pipelined.  A smaller ring runs serial windows of index_window - lookahead
+    batches, each built on the step stream right before its steps.
+
+    Pipelined, a ring of one batch cannot hold a step's own batch beside the next one's lists:
+    refused unless the epoch is that one batch (nb: the epoch's batches, None: not known)."""
+    ring, look = int(index_window), 1 if pipelined else 0
+    if ring < 1:
+        raise ValueError(f"index_window must be at least 1, got {ring}")
+    if look and ring < 2 and nb != 1:
+        raise ValueError(
+            "dp_xchg='p2p_pipe' needs an index_window of at least 2: every step reads the row "
+            "lists of the batch after its own (a lookahead of one batch), so one slot cannot "
+            "hold a step's index")
+    overlap = bool(index_overlap) and ring >= 2 + look
+    if overlap:
+        # half the ring each for the window in flight and the build beside it; pipelined, the
+        # window gives one slot to its lookahead batch (2 * window + 1 <= index_window)
+        win = ring // 2 - look
+    else:
+        win = ring - look
+    return IndexSchedule(overlap, max(1, win), look)
+
+
 class DeviceSplit:
     """One split's CSR + entity ids in HBM (int32; values kept only if not all 1.0)."""
 
@@ -163,6 +199,8 @@ class TrainEngine:
         # and a run whose first batch the previous step did not push starts with
         # rae_p2p_prologue (_p2p_start)
         self._pipe = self._p2p and xchg == "p2p_pipe"
+        if self._pipe and int(index_window) == 1:    # refused before any plan or peer exists
+            resolve_index_schedule(1, index_overlap, True, self.nb)
         self._p2p_next = None        # batch the last queued step pushed rows for (signal out)
         self._p2p_valid = False      # ... pushed from the current negatives' lists
         self._ipc_bases = {}         # handle bytes -> this process's mapping of a peer allocation
@@ -231,18 +269,16 @@ class TrainEngine:
         # run() then sets the cursor again (cursor_moved() forces the same).
         self._cursor_at = None
         self._moves_seen = self._moves()
-        # index_overlap: run() builds the next window's row index on a lowest-priority side
-        # stream while the current window's steps run (the index is parameter independent; a
-        # batch's slot is batch % index_window, so windows of half the ring never touch the
-        # slots the steps in flight read).  Otherwise each window is built on the step stream
-        # right before its steps.
-        self.index_overlap = bool(index_overlap) and self.index_window >= 2
-        self._win = self.index_window // 2 if self.index_overlap else self.index_window
-        # pipelined p2p: each window's index covers one batch more (the last step's next
-        # batch), so the ring holds a window + 1 beside the next window's build
-        self._look = 1 if self._pipe else 0
-        if self._look:
-            self._win = max(1, self._win - 1)
+        self._set_index_schedule(index_overlap)
+
+    def _set_index_schedule(self, index_overlap: bool):
+        """index_overlap: run() builds the next window's row index on a lowest-priority side
+        stream while the current window's steps run (the index is parameter independent; a
+        batch's slot is batch % index_window).  Otherwise each window is built on the step
+        stream right before its steps.  The window and the lookahead the ring allows:
+        resolve_index_schedule."""
+        self.index_overlap, self._win, self._look = resolve_index_schedule(
+            self.index_window, index_overlap, self._pipe, self.nb)
         self._idx_stream = None
         if self.index_overlap:
             lo, _ = torch.cuda.Stream.priority_range()
@@ -592,8 +628,8 @@ class TrainEngine:
         self._graph(int(count or self.graph_chunk))
 
     def windows(self, first_batch: int, count: int):
-        """The index windows run() walks: [(first batch, batches), ...] (half the ring each
-        with index_overlap)."""
+        """The index windows run() walks: [(first batch, batches), ...] (resolve_index_schedule:
+        half the ring each with index_overlap, less the pipelined form's lookahead slot)."""
         out, b, end = [], int(first_batch), int(first_batch) + int(count)
         while b < end:
             n = min(self._win, end - b)
@@ -753,8 +789,8 @@ class TrainEngine:
         already built -- on the side stream, behind everything queued on the step stream so
         far (or, `after` given, behind that event of the step stream), in front of whatever is
         queued after.  Steps queued after the point it waits for may read batches
-        >= first_batch + count - index_window only (a window of half the ring ahead of the
-        window being run satisfies that)."""
+        >= first_batch + count - index_window only (run()'s windows satisfy that, the
+        pipelined form's lookahead batch counted in: resolve_index_schedule)."""
         if not self.index_overlap:
             raise RuntimeError("prefetch_index needs index_overlap")
         x, y = int(first_batch), int(first_batch) + int(count)

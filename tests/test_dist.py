@@ -340,7 +340,8 @@ def test_gpu_p2p_delayed_rank(built_lib, cuda_dev, tmp_path, xchg):
     ("rescal+sp", 4, 1, 0, "p2p"), ("sp", 8, 4, 0, "p2p"), ("sp", 2, 2, 4, "p2p"),
     ("sp", 2, 1, 0, "p2p_pipe"), ("sp", 4, 4, 0, "p2p_pipe"), ("rescal", 2, 1, 0, "p2p_pipe"),
     ("rescal+sp", 4, 1, 0, "p2p_pipe"), ("sp", 8, 4, 0, "p2p_pipe"), ("sp", 2, 2, 4, "p2p_pipe"),
-    ("sp", 2, 4, 6, "p2p_pipe")])
+    ("sp", 2, 4, 6, "p2p_pipe"), ("sp", 2, 1, 2, "p2p_pipe"), ("sp", 2, 2, 3, "p2p_pipe"),
+    ("sp", 2, 4, 5, "p2p_pipe")])
 def test_gpu_p2p_exchange(built_lib, cuda_dev, tmp_path, decoder, ws, graph_chunk, iw, xchg):
     """the partitioned update over the peer-to-peer exchange (include/rae.h
     RAE_XCHG_P2P, csrc/rae_p2p.hpp) -- owners store the rows each peer's next batch reads into
@@ -353,7 +354,10 @@ def test_gpu_p2p_exchange(built_lib, cuda_dev, tmp_path, decoder, ws, graph_chun
     p2p_pipe (RAE_XCHG_P2P_PIPE): the next batch's rows leave during the step -- those the
     update leaves unchanged right after the forward, the updated ones from the row tasks --
     with the lookahead of one batch past every window (ring of 4 / 6: windows of one and two
-    batches, the next window's index built beside the steps) and a prologue per epoch."""
+    batches, the next window's index built beside the steps; ring of 3 / 5: the smallest rings
+    that hold a window of one, its lookahead batch and the side build; ring of 2: no room for a
+    side build, serial windows of one step -- engine.resolve_index_schedule) and a prologue per
+    epoch."""
     _launch(["gpu", str(tmp_path), decoder, "partitioned", "auto", "auto", str(iw), xchg,
              str(graph_chunk)], nproc=ws, timeout=420)
     _launch(["gpu", str(tmp_path), decoder, "replicated", "auto", "auto", str(iw)], nproc=ws)

@@ -172,14 +172,15 @@ def test_index_overlap_matches_serial(built_lib, cuda_dev, dec):
     """engine.run builds the next window's row index on a lowest-priority side stream while the
     current window's steps run (index_overlap; windows of half the ring).  A ring of 8 batches
     over two epochs (many windows, every side build behind the step stream's queue), serial
-    windows of 8, and one window per epoch train bit-identically; so does a run cut into
-    per-batch runs (frequentEval mode 2's pattern: every window already built by the last
-    run's prefetch)."""
+    windows of 8, one window per epoch, and rings of 2, 3 and 5 batches (windows of one, one and
+    two: the smallest rings, and an odd one with a slot to spare) train bit-identically; so does
+    a run cut into per-batch runs (frequentEval mode 2's pattern: every window already built by
+    the last run's prefetch)."""
     import torch
     from rae.data import synthetic_dataset
     from rae.inducer import ReconstructInducer
     out = []
-    for iw, ov in ((8, True), (8, False), (0, True)):
+    for iw, ov in ((8, True), (8, False), (0, True), (2, True), (3, True), (5, True)):
         data, gold = synthetic_dataset(1500, 3000, 10, seed=31)
         ind = ReconstructInducer(data, gold, np.random.RandomState(2), 2, 0.1, 50, 24, 12, 5,
                                  0.0, 0.0, "adagrad", "ovl", dec, False, True, False, 1.0,
@@ -189,7 +190,7 @@ def test_index_overlap_matches_serial(built_lib, cuda_dev, dec):
         eng = ind.engine
         assert eng.index_overlap == ov
         if iw:
-            assert eng.index_window == 8
+            assert eng.index_window == iw
             assert len(eng.windows(0, eng.nb)) >= (6 if ov else 3)
         out.append((_params(ind), np.array(ind.epoch_costs)))
     # per-batch runs (eager, as frequentEval mode 2 runs them) on a fresh model

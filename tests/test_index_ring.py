@@ -2,7 +2,7 @@
 prefetch_index's range arithmetic) -- no GPU: a bare engine object with the ring's fields."""
 import pytest
 
-from rae.engine import TrainEngine
+from rae.engine import TrainEngine, resolve_index_schedule
 
 
 class _Ev:
@@ -12,8 +12,7 @@ class _Ev:
 def _eng(iw=8):
     e = TrainEngine.__new__(TrainEngine)
     e.index_window = iw
-    e.index_overlap = True
-    e._win = iw // 2
+    e.index_overlap, e._win, e._look = resolve_index_schedule(iw, True, False)
     e._ready = None
     e._neg_version = 0
     return e
