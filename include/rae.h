@@ -716,6 +716,52 @@ typedef struct rae_ftopk_args {
 int64_t rae_feature_topk_workspace_bytes(const rae_ftopk_args* a);
 int rae_feature_topk(const rae_ftopk_args* a, rae_stream_t stream);
 
+/* --- cluster exemplars: a cluster's clearest and its boundary rows (no reference counterpart) --- */
+/* Plan-free and stream-ordered like the entries above: every pointer is a device pointer except
+ * the struct itself, no allocation, no synchronisation (capturable), arguments checked before the
+ * first HIP call; they write only their outputs and the workspace.                          */
+
+/* rae_label with the encoder's confidence.  Argument rules and shape limits are rae_label's
+ * (relations in [1, 512], a multiple of 4 above 128; W / Wb 16-byte aligned when relations % 4
+ * == 0), with row0 >= 0 and 0 <= nrows < 2^31 checked; nrows == 0 writes nothing.  margin_out and
+ * pmax_out may each be NULL.  Per row i of [row0, row0+nrows), stored at index i - row0, with
+ * S = x W + Wb as rae_label computes it (bitwise):
+ *   labels_out  rae_label's label: the first maximum of S, NaN counting as the maximum.
+ *   margin_out  S[label] - S[second], one fp32 subtraction; second is the best column among
+ *               k != label by the same rule.  relations == 1: +inf.  NaN whenever the subtraction
+ *               is (a NaN logit, inf - inf); otherwise >= 0, and 0 on a tie.
+ *   pmax_out    bitwise the value rae_label stores at probs[i, label].
+ * A row's three outputs are a function of the row and W, Wb, relations alone: bitwise independent
+ * of row0, nrows and the other rows.                                                         */
+int rae_label_stats(const int32_t* indptr, const int32_t* indices, const float* values,
+                    const float* W, const float* Wb, int32_t relations,
+                    int64_t row0, int64_t nrows, int64_t* labels_out, float* margin_out,
+                    float* pmax_out, rae_stream_t stream);
+
+/* Per cluster c the `top` rows by a per-row score.  The candidates of cluster c are the rows i in
+ * [0, nrows) with labels[i] == c whose score is not NaN; rows with a label outside [0, relations)
+ * are skipped (never an out-of-range access); -0.0f counts and is returned as +0.0f, +-inf are
+ * ordinary scores.  Row c of rows_out / scores_out ((relations, top)) is its candidates by score --
+ * descending for largest == 1, ascending for largest == 0 -- then row index ascending (a total
+ * order: the output is unique), cut to `top` and padded with (-1, -inf) for either order.  The
+ * returned scores are bitwise the input scores (-0 -> +0 aside); rows_out indexes the call's rows,
+ * 0 ... nrows - 1.  0 <= nrows < 2^31 (0: all padding; labels / scores may then be NULL),
+ * 1 <= relations <= 512, 1 <= top <= 32 (top above a cluster's size is valid).  labels and scores
+ * need their element alignment only.  The result is bitwise independent of the launch
+ * decomposition, which is a function of (nrows, relations, top) alone.                      */
+typedef struct rae_exemplar_args {
+    const int64_t* labels; const float* scores; int64_t nrows;   /* 0 <= nrows < 2^31           */
+    int32_t relations;                            /* 1..512                                      */
+    int32_t top;                                  /* 1..32                                       */
+    int32_t largest;                              /* 1: highest scores first   0: lowest first   */
+    int32_t* rows_out; float* scores_out;         /* (relations, top); scores_out may be NULL    */
+    void* workspace; int64_t workspace_bytes;     /* 256-byte aligned                            */
+} rae_exemplar_args;
+/* The bytes rae_cluster_exemplars needs for a's nrows, relations and top: the strips' lists, at
+ * most 128 strips x 512 x 32 keys of 8 bytes = 16 MiB.  Host only; -1 on a bad argument.    */
+int64_t rae_cluster_exemplars_workspace_bytes(const rae_exemplar_args* a);
+int rae_cluster_exemplars(const rae_exemplar_args* a, rae_stream_t stream);
+
 /* --- measurement helper (bench.py; no reference counterpart) ------------------------- */
 /* STREAM-style device copy of `bytes` (multiple of 16, 16-byte aligned pointers) with float4
  * loads and stores: the measured HBM ceiling bench.py reports next to the 8 TB/s spec.   */

@@ -39,6 +39,7 @@
 #include "rae_relscore.hpp"
 #include "rae_topk.hpp"
 #include "rae_feature.hpp"
+#include "rae_exemplar.hpp"
 #include "rae_sampler.hpp"
 #include "rae_sp.hpp"
 #include "rae_step.hpp"
@@ -2403,6 +2404,97 @@ extern "C" int rae_feature_topk(const rae_ftopk_args* a, rae_stream_t stream) {
     hipLaunchKernelGGL(k_ftopk_finish, dim3((unsigned)ceil_div((int)a->relations, RAE_FT_FQ)),
                        dim3(RAE_FT_FQ * 64), 0, st, (const rae_key64*)k.keys, L.strips,
                        (int)a->relations, (int)a->top, a->feats_out, a->scores_out);
+    HIPCHK(hipGetLastError());
+    return RAE_OK;
+}
+
+// ---- cluster exemplars (rae_exemplar.hpp) -------------------------------------------------------
+extern "C" int rae_label_stats(const int32_t* indptr, const int32_t* indices, const float* values,
+                               const float* W, const float* Wb, int32_t relations, int64_t row0,
+                               int64_t nrows, int64_t* labels_out, float* margin_out,
+                               float* pmax_out, rae_stream_t stream) {
+    if (const int rc = not_null({{indptr, "indptr"}, {indices, "indices"}, {W, "W"}, {Wb, "Wb"},
+                                 {labels_out, "labels_out"}}))
+        return rc;
+    const int m = relations;
+    if (m < 1 || m > 512) return fail(RAE_E_INVALID, "relations must be in [1, 512] for labelling");
+    const bool v4 = (m % 4) == 0;
+    if (!v4 && m > 128)
+        return fail(RAE_E_INVALID, "relations must be a multiple of 4 above 128 for labelling");
+    if (row0 < 0) return fail(RAE_E_INVALID, "row0 must be >= 0");
+    if (const int rc = count_range("nrows", nrows, 0)) return rc;
+    if (v4)
+        if (const int rc = aligned({W, Wb}, 15, "W / Wb must be 16-byte aligned")) return rc;
+    if (const int rc = aligned({indptr, indices, values, W, Wb, margin_out, pmax_out}, 3,
+                               "indptr / indices / values / W / Wb / margin_out / pmax_out must be "
+                               "4-byte aligned"))
+        return rc;
+    if (const int rc = aligned({labels_out}, 7, "labels_out must be 8-byte aligned")) return rc;
+    if (nrows == 0) return RAE_OK;
+    const int64_t blocks = std::min<int64_t>((nrows + RAE_NWAVE - 1) / RAE_NWAVE, 65536);
+    with_bool(v4, [&](auto Vf) {
+        hipLaunchKernelGGL(k_label_stats<RAE_CV(Vf)>, dim3((unsigned)blocks), dim3(RAE_BT), 0,
+                           (hipStream_t)stream, indptr, indices, values, W, Wb, m, row0, nrows,
+                           labels_out, margin_out, pmax_out);
+    });
+    HIPCHK(hipGetLastError());
+    return RAE_OK;
+}
+
+namespace {
+struct CexLayout { size_t total; int strips, waves; };
+// shapes of rae_cluster_exemplars and its workspace layout (host only)
+int cex_layout(const rae_exemplar_args* a, CexLayout& L) {
+    if (!a) return fail(RAE_E_INVALID, "null argument");
+    if (const int rc = count_range("nrows", a->nrows, 0)) return rc;
+    if (const int rc = relations_range(a->relations)) return rc;
+    if (a->top < 1 || a->top > RAE_CX_MAXTOP) return fail(RAE_E_INVALID, "top must be in [1, 32]");
+    if (a->largest != 0 && a->largest != 1) return fail(RAE_E_INVALID, "largest must be 0 or 1");
+    L.strips = cex_strips(a->nrows);
+    L.waves = cex_waves(a->relations, a->top);
+    L.total = ev_align((size_t)L.strips * (size_t)a->relations * (size_t)a->top * sizeof(rae_key64));
+    return RAE_OK;
+}
+}  // namespace
+
+extern "C" int64_t rae_cluster_exemplars_workspace_bytes(const rae_exemplar_args* a) {
+    CexLayout L;
+    if (cex_layout(a, L)) return -1;
+    return (int64_t)L.total;
+}
+
+extern "C" int rae_cluster_exemplars(const rae_exemplar_args* a, rae_stream_t stream) {
+    CexLayout L;
+    if (const int rc = cex_layout(a, L)) return rc;
+    if (a->nrows > 0)
+        if (const int rc = not_null({{a->labels, "labels"}, {a->scores, "scores"}})) return rc;
+    if (!a->rows_out) return fail(RAE_E_INVALID, "rows_out is NULL");
+    const char* al = "labels / scores / rows_out / scores_out must be aligned to their element size";
+    if (const int rc = aligned({a->labels}, 7, al)) return rc;
+    if (const int rc = aligned({a->scores, a->rows_out, a->scores_out}, 3, al)) return rc;
+    if (const int rc = check_workspace(a->workspace, a->workspace_bytes, L.total,
+                                       "rae_cluster_exemplars_workspace_bytes"))
+        return rc;
+    hipStream_t st = (hipStream_t)stream;
+    CexArgs k;
+    k.labels = (const long long*)a->labels;
+    k.scores = (const int*)a->scores;             // the scores' dwords, a bit cast
+    k.nrows = a->nrows; k.strip_rows = cex_strip_rows(a->nrows);
+    k.m = a->relations; k.top = a->top; k.negate = a->largest ? 0 : 1;
+    k.keys = (rae_key64*)a->workspace;
+    const size_t shmem = (size_t)L.waves * a->relations * a->top * sizeof(rae_key64);
+    if (shmem > 48 * 1024)       // large dynamic LDS is opted into per kernel (not a stream operation)
+        HIPCHK(hipFuncSetAttribute((const void*)k_cexemplar,
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+    hipLaunchKernelGGL(k_cexemplar, dim3((unsigned)L.strips), dim3(L.waves * 64), shmem, st, k);
+    hipLaunchKernelGGL(k_ftopk_finish, dim3((unsigned)ceil_div((int)a->relations, RAE_FT_FQ)),
+                       dim3(RAE_FT_FQ * 64), 0, st, (const rae_key64*)k.keys, L.strips,
+                       (int)a->relations, (int)a->top, a->rows_out, a->scores_out);
+    if (k.negate && a->scores_out) {
+        const int n = a->relations * a->top;
+        hipLaunchKernelGGL(k_cex_negate, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st,
+                           (const int32_t*)a->rows_out, a->scores_out, n);
+    }
     HIPCHK(hipGetLastError());
     return RAE_OK;
 }

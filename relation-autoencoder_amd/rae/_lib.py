@@ -86,6 +86,7 @@ EXPORTS = (
     "rae_cluster_count", "rae_b3_metrics",
     "rae_row_keys", "rae_cluster_key_count", "rae_cluster_topk",
     "rae_feature_support", "rae_feature_topk", "rae_feature_topk_workspace_bytes",
+    "rae_label_stats", "rae_cluster_exemplars", "rae_cluster_exemplars_workspace_bytes",
 )
 RAE_IPC_HANDLE_BYTES = 64
 # rae_index_dims' values in order, and rae_index_read's regions (include/rae.h RAE_IDXR_*)
@@ -256,6 +257,31 @@ def ftopk_strip_rows(d: int) -> int:
     return -(-(-(-int(d) // ftopk_strips(d))) // step) * step
 
 
+class RaeExemplarArgs(C.Structure):
+    """rae_exemplar_args (include/rae.h): per cluster the `top` rows by a per-row score."""
+    _fields_ = [
+        ("labels", _P), ("scores", _P), ("nrows", C.c_int64), ("relations", C.c_int32),
+        ("top", C.c_int32), ("largest", C.c_int32), ("rows_out", _P), ("scores_out", _P),
+        ("workspace", _P), ("workspace_bytes", C.c_int64),
+    ]
+
+
+# rae_cluster_exemplars: largest `top` and the decomposition (csrc/rae_exemplar.hpp RAE_CX_*):
+# shortest strip, most strips, the LDS a workgroup of several waves keeps its lists within
+RAE_CX_MAXTOP, RAE_CX_STRIP_ROWS, RAE_CX_MAXSTRIPS, RAE_CX_LDS_WG = 32, 4096, 128, 64 * 1024
+
+
+def cex_strips(nrows: int) -> int:
+    """The strips rae_cluster_exemplars cuts nrows rows into (csrc/rae_exemplar.hpp cex_strips)."""
+    return max(1, min(RAE_CX_MAXSTRIPS, -(-int(nrows) // RAE_CX_STRIP_ROWS)))
+
+
+def cex_waves(relations: int, top: int) -> int:
+    """Waves per workgroup of k_cexemplar: the most of 4, 2, 1 whose lists fit 64 KiB."""
+    lb = int(relations) * int(top) * 8
+    return 4 if 4 * lb <= RAE_CX_LDS_WG else (2 if 2 * lb <= RAE_CX_LDS_WG else 1)
+
+
 LABEL_MODES = ("encoder", "decoder", "joint")
 
 
@@ -373,6 +399,13 @@ def load(path: str | None = None):
     lib.rae_feature_topk_workspace_bytes.restype = C.c_int64
     lib.rae_feature_topk.argtypes = [C.POINTER(RaeFtopkArgs), _P]
     lib.rae_feature_topk.restype = C.c_int
+    lib.rae_label_stats.argtypes = [_P, _P, _P, _P, _P, C.c_int32, C.c_int64, C.c_int64, _P, _P,
+                                    _P, _P]
+    lib.rae_label_stats.restype = C.c_int
+    lib.rae_cluster_exemplars_workspace_bytes.argtypes = [C.POINTER(RaeExemplarArgs)]
+    lib.rae_cluster_exemplars_workspace_bytes.restype = C.c_int64
+    lib.rae_cluster_exemplars.argtypes = [C.POINTER(RaeExemplarArgs), _P]
+    lib.rae_cluster_exemplars.restype = C.c_int
     lib.rae_neg_sample.argtypes = [_P, C.c_int64, _P, C.c_int64, _P, _P]
     lib.rae_neg_sample_philox.argtypes = [_P, C.c_int64, C.c_uint64, C.c_uint64, C.c_int64, _P, _P]
     lib.rae_time_next.argtypes = [_P, _P, _P]

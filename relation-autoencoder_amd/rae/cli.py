@@ -94,6 +94,22 @@ def get_command_args(argv=None, program_name="rae"):
                         "(a rare feature carries a large, meaningless weight)")
     p.add_argument("--print-features-raw", dest="print_features_raw", action="store_true",
                    help="--print-features ranks by W[f, k] itself, not the row-centred weight")
+    p.add_argument("--print-exemplars", dest="print_exemplars", type=int, nargs="?",
+                   const=5, default=0, metavar="N",
+                   help="after each evaluation print every induced relation's N (default 5, "
+                        "1..32) most confident rows of the evaluated splits as "
+                        "row:e1 | trigger | e2:score.  Always over the encoder's own labels, "
+                        "whatever --label-with is: the margin is the encoder's statement about "
+                        "its own argmax")
+    p.add_argument("--print-exemplars-order", dest="print_exemplars_order", default="most",
+                   choices=("most", "least", "both"),
+                   help="--print-exemplars lists the most confident rows of a relation, the "
+                        "least confident (its boundary), or both")
+    p.add_argument("--print-exemplars-by", dest="print_exemplars_by", default="margin",
+                   choices=("margin", "pmax"),
+                   help="--print-exemplars ranks by the encoder's logit margin (best minus "
+                        "second-best logit: it still separates rows whose posterior is 1.0) or "
+                        "by its posterior of the label")
     p.add_argument("--predict-arguments", dest="predict_arguments", type=int, default=0,
                    metavar="ROWS",
                    help="after the last epoch print the model's top predictions for both "
@@ -203,7 +219,10 @@ def main(argv=None):
                              predict_relations=args.predict_relations,
                              print_features=args.print_features,
                              print_features_min_count=args.print_features_min_count,
-                             print_features_raw=args.print_features_raw)
+                             print_features_raw=args.print_features_raw,
+                             print_exemplars=args.print_exemplars,
+                             print_exemplars_order=args.print_exemplars_order,
+                             print_exemplars_by=args.print_exemplars_by)
     if exchange is not None:
         ind.compile_function()
         rdist.warm_up(exchange, ind.engine.exchange_buf)

@@ -43,6 +43,7 @@ ClusterResult = collections.namedtuple("ClusterResult",
 # TrainEngine.cluster_profiles' result: per cluster the `top` most frequent keys and their counts,
 # both (relations, top) numpy int32, padded with (-1, 0) (rae.evaluation.topk_from_table's order)
 ProfileResult = collections.namedtuple("ProfileResult", "keys counts")
+ExemplarResult = collections.namedtuple("ExemplarResult", "rows scores")
 
 
 def _upload_graph(g, stream):
@@ -1536,3 +1537,130 @@ class TrainEngine:
         a.feats_out, a.scores_out = _lib.ptr(feats), _lib.ptr(scores)
         _lib.check(self.lib.rae_feature_topk(C.byref(a), self._stream()), "rae_feature_topk")
         return feats, scores
+
+    # ------------------------------------------------------------------ cluster exemplars
+    def _row_range(self, split: DeviceSplit, row0, nrows):
+        row0 = int(row0)
+        nrows = split.N - row0 if nrows is None else int(nrows)
+        if row0 < 0 or nrows < 0 or row0 + nrows > split.N:
+            raise IndexError(f"rows [{row0}, {row0 + nrows}) out of the split's {split.N}")
+        return row0, nrows
+
+    def label_stats(self, split: DeviceSplit, row0: int = 0, nrows: int | None = None):
+        """The encoder's labels with its confidence in them (rae_label_stats) for rows
+        [row0, row0+nrows) of `split` at the current W / Wb: device tensors (labels int64, margin
+        fp32, pmax fp32).  labels and pmax are bitwise label()'s labels and probs[i, label]; margin
+        is the logit margin S[label] - S[second], what still separates rows whose posterior has
+        saturated at 1.0f.  rae.evaluation.label_stats is the host oracle.  Queued on the current
+        stream, no host synchronisation; partitioned update with stale rows: gathers W first (a
+        collective, like label)."""
+        if self.stale(accumulators=False):
+            self.sync_replicas(accumulators=False)
+        row0, nrows = self._row_range(split, row0, nrows)
+        lab = torch.empty(nrows, dtype=torch.int64, device=self.device)
+        margin = torch.empty(nrows, dtype=torch.float32, device=self.device)
+        pmax = torch.empty(nrows, dtype=torch.float32, device=self.device)
+        self._queue_label_stats(split, row0, nrows, lab, margin, pmax)
+        return lab, margin, pmax
+
+    def _queue_label_stats(self, split, row0, nrows, lab, margin, pmax):
+        if nrows == 0:
+            return
+        W, Wb = self.model.params[0], self.model.params[1]
+        _lib.check(self.lib.rae_label_stats(
+            C.c_void_p(split.indptr.data_ptr()), C.c_void_p(split.indices.data_ptr()),
+            C.c_void_p(split.values.data_ptr()) if split.values is not None else None,
+            C.c_void_p(W.data_ptr()), C.c_void_p(Wb.data_ptr()), self.m, row0, nrows,
+            _lib.ptr(lab), _lib.ptr(margin), _lib.ptr(pmax), self._stream()), "rae_label_stats")
+
+    def queue_cluster_exemplars(self, split: DeviceSplit, top: int = 5, by="margin",
+                                largest: bool = True, labels=None, row0: int = 0,
+                                nrows: int | None = None):
+        """Queue rae_label_stats (unless `by` is a tensor and labels are given) ->
+        rae_cluster_exemplars for rows [row0, row0+nrows) of `split` on the current stream (no host
+        synchronisation).  by: "margin" or "pmax" of the encoder, or a device float tensor of nrows
+        per-row scores (psi / J of eval_relations, a term of evaluate(terms=True), ...).  labels:
+        a device int64 tensor of nrows cluster ids (default: the encoder's own).  The result lands
+        in self._cx_out (int32 words: [0 : relations * top] the rows within the range,
+        [relations * 32 : relations * 32 + relations * top] the scores' bits)."""
+        row0, nrows = self._row_range(split, row0, nrows)
+        top = self._check_top(top)
+        scores = None
+        if torch.is_tensor(by):
+            scores = by.to(device=self.device, dtype=torch.float32).contiguous().reshape(-1)
+            if scores.numel() != nrows:
+                raise ValueError(f"by has {scores.numel()} scores, the range {nrows} rows")
+        elif by not in ("margin", "pmax"):
+            raise ValueError('by must be "margin", "pmax" or a device tensor of per-row scores')
+        if labels is not None:
+            labels = labels.to(device=self.device, dtype=torch.int64).contiguous().reshape(-1)
+            if labels.numel() != nrows:
+                raise ValueError(f"labels has {labels.numel()} entries, the range {nrows} rows")
+        if scores is None or labels is None:
+            lab = torch.empty(nrows, dtype=torch.int64, device=self.device)
+            st = torch.empty(nrows, dtype=torch.float32, device=self.device)
+            if scores is None:
+                self._queue_label_stats(split, row0, nrows, lab, st if by == "margin" else None,
+                                        st if by == "pmax" else None)
+                scores = st
+            else:
+                self._queue_label_stats(split, row0, nrows, lab, None, None)
+            labels = lab if labels is None else labels
+        half = self.m * _lib.RAE_CX_MAXTOP
+        if getattr(self, "_cx_out", None) is None:       # once per engine
+            self._cx_out = torch.zeros(2 * half, dtype=torch.int32, device=self.device)
+        a = _lib.RaeExemplarArgs()
+        a.relations, a.largest = self.m, 1
+        a.nrows, a.top = (1 << 31) - 1, _lib.RAE_CX_MAXTOP     # the workspace: sized for every call
+        self._workspace(a, "_cx_ws", "rae_cluster_exemplars_workspace_bytes",
+                        lambda: self.lib.rae_cluster_exemplars_workspace_bytes(C.byref(a)))
+        a.nrows, a.top, a.largest = nrows, top, int(bool(largest))
+        a.labels, a.scores = _lib.ptr(labels) or None, _lib.ptr(scores) or None
+        a.rows_out = self._cx_out.data_ptr()
+        a.scores_out = self._cx_out.data_ptr() + 4 * half
+        _lib.check(self.lib.rae_cluster_exemplars(C.byref(a), self._stream()),
+                   "rae_cluster_exemplars")
+        self._cx_keep = (labels, scores)     # alive until the queued kernels have read them
+
+    def cluster_exemplars(self, split: DeviceSplit, top: int = 5, by="margin",
+                          largest: bool = True, labels=None, row0: int = 0,
+                          nrows: int | None = None):
+        """Per induced cluster its `top` rows by a per-row score, all on the device:
+        ExemplarResult(rows, scores), rows (relations, top) int32 row ids of the split (row0 added;
+        padding -1), scores (relations, top) fp32 -- score descending (largest) or ascending, then
+        row ascending, padded with (-1, -inf).  by="margin": the clearest members of every cluster
+        (largest) or its boundary rows (largest=False) by the encoder's logit margin; "pmax" by its
+        posterior; a device tensor: any per-row score.  rae.evaluation.cluster_exemplars is the
+        host oracle.  One read-back of 2 * relations * 32 words.  Touches no training state.
+        Partitioned update with stale rows: gathers W first (a collective, like label)."""
+        if self.stale(accumulators=False):
+            self.sync_replicas(accumulators=False)
+        self.queue_cluster_exemplars(split, top, by, largest, labels, row0, nrows)
+        top = int(top)
+        host = self._cx_out.cpu().numpy()
+        self._cx_keep = None
+        half, n = self.m * _lib.RAE_CX_MAXTOP, self.m * top
+        rows = host[:n].reshape(self.m, top).copy()
+        rows[rows >= 0] += int(row0)
+        return ExemplarResult(rows, host[half:half + n].view(np.float32).reshape(self.m, top).copy())
+
+    def cluster_confidence(self, split: DeviceSplit, bins: int = 10, row0: int = 0,
+                           nrows: int | None = None):
+        """Per induced cluster the histogram of its rows' posterior pmax: a (relations, bins)
+        int32 device tensor, bin = min(int(pmax * bins), bins - 1) (a NaN pmax is not counted).
+        rae_label_stats, the binning in torch on the device, then the existing
+        rae_cluster_key_count with the bin as the per-row key: no kernel of its own.  A collapsed
+        encoder shows as one row of the table holding every count."""
+        bins = int(bins)
+        if not 1 <= bins <= _lib.RAE_KEYCOUNT_MAX_KEYS:
+            raise ValueError(f"bins must be in [1, {_lib.RAE_KEYCOUNT_MAX_KEYS}]")
+        lab, _, pmax = self.label_stats(split, row0, nrows)
+        n = int(lab.numel())
+        key = torch.clamp((pmax * bins).to(torch.int32), max=bins - 1)
+        key = torch.where(torch.isnan(pmax), torch.full_like(key, -1), key).contiguous()
+        table = torch.zeros((self.m, bins), dtype=torch.int32, device=self.device)
+        if n:
+            _lib.check(self.lib.rae_cluster_key_count(
+                C.c_void_p(lab.data_ptr()), C.c_void_p(key.data_ptr()), n, self.m, bins, 0,
+                C.c_void_p(table.data_ptr()), self._stream()), "rae_cluster_key_count")
+        return table

@@ -477,6 +477,88 @@ def format_relation_features(feats, scores, support, names=None):
     return lines
 
 
+# ------------------------------------------------------------------ cluster exemplars
+def label_stats(X, W, Wb, dtype=np.float32):
+    """The host oracle of rae_label_stats: (labels int64, margin, pmax) of every row of the CSR
+    matrix X with S = X W + Wb computed in `dtype` (float32: the device's formats; float64: the
+    reference a rounding bound is measured against).
+      labels  np.argmax: the first maximum, NaN counting as the maximum.
+      margin  S[label] - S[second], second the argmax over the columns k != label; +inf with one
+              relation; NaN whenever the subtraction is (a NaN logit, inf - inf).
+      pmax    exp(S[label] - best) / sum_k exp(S[k] - best), best = S[label]."""
+    W = np.asarray(W, dtype=dtype)
+    Wb = np.asarray(Wb, dtype=dtype).reshape(-1)
+    N, m = X.shape[0], W.shape[1]
+    with np.errstate(invalid="ignore", over="ignore"):
+        S = np.asarray(X.astype(dtype) @ W, dtype=dtype).reshape(N, m) + Wb[None, :]
+        rows = np.arange(N)
+        labels = np.argmax(S, axis=1).astype(np.int64) if N else np.zeros(0, np.int64)
+        best = S[rows, labels]
+        if m == 1:
+            margin = np.full(N, np.inf, dtype=dtype)
+        else:
+            own = np.zeros(S.shape, dtype=bool)
+            own[rows, labels] = True
+            nan = np.isnan(S)
+            # the maximum over the other columns, NaN counting as the maximum
+            second = np.where((nan & ~own).any(axis=1), np.nan,
+                              np.where(own | nan, -np.inf, S).max(axis=1)).astype(dtype)
+            margin = (best - second).astype(dtype)
+        e = np.exp((S - best[:, None]).astype(dtype)).astype(dtype)
+        pmax = (np.exp((best - best).astype(dtype)).astype(dtype) / e.sum(axis=1, dtype=dtype))
+    return labels, margin.astype(dtype), pmax.astype(dtype)
+
+
+def cluster_exemplars(labels, scores, relations, top, largest=True):
+    """The host oracle of rae_cluster_exemplars: (rows int32, scores float32), both (relations,
+    top).  Row c: the rows i with labels[i] == c whose score is not NaN, by score (descending for
+    largest, else ascending), then row ascending, cut to `top` and padded with (-1, -inf).  -0.0 is
+    +0.0, in the order and in the output; labels outside [0, relations) are skipped."""
+    labels = np.asarray(labels).astype(np.int64).reshape(-1)
+    s = np.asarray(scores, dtype=np.float32).reshape(-1)
+    s = np.where(s == 0, np.float32(0), s)                    # -0 -> +0
+    relations, top = int(relations), int(top)
+    rows_out = np.full((relations, top), -1, dtype=np.int32)
+    scores_out = np.full((relations, top), -np.inf, dtype=np.float32)
+    cand = np.flatnonzero((labels >= 0) & (labels < relations) & ~np.isnan(s))
+    order = cand[np.lexsort((cand, -s[cand] if largest else s[cand], labels[cand]))]
+    lab = labels[order]
+    start = np.searchsorted(lab, np.arange(relations), side="left")
+    stop = np.searchsorted(lab, np.arange(relations), side="right")
+    for c in range(relations):
+        take = order[start[c]:min(stop[c], start[c] + top)]
+        rows_out[c, :take.shape[0]] = take
+        scores_out[c, :take.shape[0]] = s[take]
+    return rows_out, scores_out
+
+
+def format_cluster_exemplars(rows, scores, sizes, args1, args2, entity_names=None, row_keys=None,
+                             key_names=None):
+    """rows / scores (m, top) of TrainEngine.cluster_exemplars -> one line per relation:
+    'relation k (n rows): row:e1 | trigger | e2:score ...', first exemplar first; n = sizes[k].
+    e1 / e2 are args1[row] / args2[row] through entity_name; the trigger is key_names[row_keys[row]]
+    ('-' for a row without a key) and is omitted with its bars when row_keys is None.  Padding is
+    not printed."""
+    rows, scores = np.asarray(rows), np.asarray(scores)
+    lines = []
+    for k in range(rows.shape[0]):
+        items = []
+        for i, s in zip(rows[k], scores[k]):
+            if i < 0:
+                continue
+            i = int(i)
+            mid = ""
+            if row_keys is not None:
+                key = int(row_keys[i])
+                name = "-" if key < 0 else (str(key) if key_names is None else str(key_names[key]))
+                mid = " {} |".format(name)
+            items.append("{}:{} |{} {}:{:.9g}".format(                # %.9g round-trips a float32
+                i, entity_name(entity_names, args1[i]), mid,
+                entity_name(entity_names, args2[i]), float(s)))
+        lines.append("relation {} ({} rows): {}".format(k, int(sizes[k]), " ".join(items)).rstrip())
+    return lines
+
+
 # ------------------------------------------------------------------ relation scores from the decoder
 def relation_scores(params, decoder, e1, e2):
     """psi (nq, m) float64, the oracle of rae_relation_scores: the decoder's score of every

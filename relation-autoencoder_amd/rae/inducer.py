@@ -14,7 +14,8 @@ import torch
 from .data import SPLIT_LABELS
 from .engine import DeviceSplit, TrainEngine
 from .evaluation import (GoldIndex, KeyIndex, construct_split_evaluator,
-                         format_argument_predictions, format_cluster_profiles,
+                         format_argument_predictions, format_cluster_exemplars,
+                         format_cluster_profiles,
                          format_relation_features, format_relation_predictions,
                          format_relation_preferences, key_table, row_keys, topk_from_table)
 from .model import OieModelFunctions, _as_bool, make_optimizer
@@ -81,7 +82,8 @@ class ReconstructInducer:
                  print_top=5, print_by="trigger", eval_rank=False, eval_rank_ks=(1, 10, 100),
                  eval_rank_rows=None, print_preferences=0, predict_arguments=0, predict_top=10,
                  label_with="encoder", predict_relations=0, print_features=0,
-                 print_features_min_count=5, print_features_raw=False):
+                 print_features_min_count=5, print_features_raw=False, print_exemplars=0,
+                 print_exemplars_order="most", print_exemplars_by="margin"):
         if label_with not in ("encoder", "decoder", "joint"):
             raise ValueError("label_with must be 'encoder', 'decoder' or 'joint'")
         if int(predict_relations) < 0:
@@ -90,6 +92,12 @@ class ReconstructInducer:
             raise ValueError("print_features must be in [0, 32] (0: off)")
         if int(print_features_min_count) < 0:
             raise ValueError("print_features_min_count must be >= 0")
+        if not 0 <= int(print_exemplars) <= 32:
+            raise ValueError("print_exemplars must be in [0, 32] (0: off)")
+        if print_exemplars_order not in ("most", "least", "both"):
+            raise ValueError("print_exemplars_order must be 'most', 'least' or 'both'")
+        if print_exemplars_by not in ("margin", "pmax"):
+            raise ValueError("print_exemplars_by must be 'margin' or 'pmax'")
         if not 0 <= int(print_preferences) <= 32:
             raise ValueError("print_preferences must be in [0, 32] (0: off)")
         if int(predict_arguments) < 0 or not 1 <= int(predict_top) <= 32:
@@ -184,6 +192,15 @@ class ReconstructInducer:
         self.print_features = int(print_features)
         self.print_features_min_count = int(print_features_min_count)
         self.print_features_raw = bool(print_features_raw)
+        # print_exemplars: after each epoch's evaluation learn() prints, per induced relation of
+        # the evaluated splits, its N most confident rows (print_exemplars_order "least": its N
+        # boundary rows; "both": the two lists) by the encoder's logit margin (print_exemplars_by
+        # "pmax": its posterior), as row:e1 | trigger | e2:score (TrainEngine.cluster_exemplars).
+        # Always over the ENCODER's own labels, whatever label_with is: the margin is the
+        # encoder's statement about its own argmax
+        self.print_exemplars = int(print_exemplars)
+        self.print_exemplars_order = print_exemplars_order
+        self.print_exemplars_by = print_exemplars_by
         # cluster_eval: where learn() scores the induced clusters -- "host": the label download
         # and the Python sets of the reference (get_clusters_sets + SingleLabelClusterEvaluation);
         # "device": the contingency table and B^3 on the GPU (TrainEngine.cluster_metrics), same
@@ -371,6 +388,11 @@ class ReconstructInducer:
                 lines = self.relation_feature_lines()
                 if verbose:
                     print("\n".join(lines))
+            if self.print_exemplars:
+                for split in (SPLIT_LABELS[:1] if self._mode() == 1 else SPLIT_LABELS[1:]):
+                    lines = self.cluster_exemplar_lines(split)
+                    if verbose:
+                        print("\n".join(lines))
         if self.predict_arguments:
             for split in (SPLIT_LABELS[:1] if self._mode() == 1 else SPLIT_LABELS[1:]):
                 lines = self.argument_prediction_lines(split)
@@ -406,6 +428,41 @@ class ReconstructInducer:
         return format_relation_features(feats.cpu().numpy(), scores.cpu().numpy(),
                                         eng.feature_support(eng.split).cpu().numpy(),
                                         lex.get_str_pruned if lex is not None else None)
+
+    def cluster_exemplar_lines(self, split):
+        """print_exemplars' lines for the rows _labels covers (the first nbs * batch_size) at the
+        current parameters: per order a header, then one line per relation
+        (rae.evaluation.format_cluster_exemplars) -- the relation's size under the encoder's
+        labels, then its exemplars as row:e1 | trigger | e2:score, the trigger from the dataset's
+        lexicon when it has one."""
+        if not self._check_for_compiled_functions():
+            self.compile_function()
+        eng, ds = self.engine, self._dev_split[split]
+        nrows = (self.data.split[split].args1.shape[0] // self.batch_size) * self.batch_size
+        lab, margin, pmax = eng.label_stats(ds, 0, nrows)
+        score = margin if self.print_exemplars_by == "margin" else pmax
+        sizes = torch.bincount(lab, minlength=self.relationNum)[:self.relationNum].cpu().numpy()
+        row_keys = key_names = None
+        if getattr(self.data, "featureLex", None) is not None:
+            ki = self._key_index.get("*")
+            if ki is None:
+                ki = self._key_index["*"] = KeyIndex.from_lexicon(self.data.featureLex)
+            if ki.n_keys > 0:
+                row_keys, key_names = eng._keys_dev(ds, ki).cpu().numpy(), ki.names
+        sp = self.data.split[split]
+        note = "" if self.label_with == "encoder" else \
+            " (the encoder's own labels, not label_with={})".format(self.label_with)
+        lines = []
+        for order in (("most", "least") if self.print_exemplars_order == "both"
+                      else (self.print_exemplars_order,)):
+            res = eng.cluster_exemplars(ds, self.print_exemplars or 5, by=score,
+                                        largest=order == "most", labels=lab, row0=0, nrows=nrows)
+            lines.append("{} exemplars, {} confident by {}{}".format(
+                split, order, self.print_exemplars_by, note))
+            lines += format_cluster_exemplars(
+                res.rows, res.scores, sizes, np.asarray(sp.args1), np.asarray(sp.args2),
+                getattr(self.data, "id2Arg", None), row_keys, key_names)
+        return lines
 
     def argument_prediction_lines(self, split):
         """predict_arguments' lines for the first predict_arguments rows of `split`: a header,
